@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X hot path: micrographs/s, denoise -> score -> NMS on 4096x4096 fp32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pipeline|extract|denoise]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pipeline|extract|denoise] [--dump-outputs DIR] [--full]
 
 One step = one synthetic 4096x4096 micrograph (N(0,1), seed 1000+i, already resident in HBM)
 through the whole path on one GPU:
@@ -16,7 +16,11 @@ then the pick tables are gathered to rank 0 over RCCL (the only collective; time
 `--gpus N` under torchrun uses the ranks it is given; run as plain `python bench.py --gpus N` it starts its own N
 rank processes (topaz_amd.parallel.launch_local_ranks), one per GPU, and rank 0 prints the line.
 
-Prints ONE JSON line (see the driver contract) including
+Prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times exactly K steps and prints the headline
+figure: `value` (micrographs/s), `ms_per_step` (one timed step), the per-rank times, the gather and the launch count.
+`--dump-outputs DIR` writes what rank 0's last timed step returned (pick_scores / pick_coords, or denoised for
+--workload denoise) as DIR/<name>.npy in float32; the inputs and weights are seeded, so two builds can be compared.
+`--full` adds, after the timed region,
   roofline     -- the dominant kernel (the conv instantiation with the most time in a step): algorithmic FLOP / HIP-event
                   time of its launches in the timed steps themselves; class aggregates, HBM-bound rows and the sustained-MFMA
                   probe from extra steps after the timed region
@@ -29,8 +33,8 @@ Prints ONE JSON line (see the driver contract) including
   configs      -- BASELINE configs 2 / 3 / 5 and the detectors users run, one by one: ms, fraction of the 2xf16 peak, launches,
                   board power and shader clock while the config runs back to back
   exact_fp32   -- the same step with every convolution pinned to the fp32-MFMA kernels (tpz_ctx_set_exact)
-  leg_seconds  -- what each leg after the timed region cost (a default run takes well under a minute)
-`--extras` adds the secondary legs (minutes): pcie_inclusive (the step fed from pinned host memory), the A/B legs
+  leg_seconds  -- what each leg after the timed region cost (a --full run takes well under a minute)
+`--extras` (implies --full) adds the secondary legs (minutes): pcie_inclusive (the step fed from pinned host memory), the A/B legs
 row_major_raster / patch_lanes_unbatched / full_patch_tensors, cli_inclusive (the CLI itself from MRC files on tmpfs) and a CPU
 baseline per config.
 `--dry-run` (CPU box, no GPU): skips the hot path and fabricates pick tables so that the launcher, the barriers and the
@@ -43,6 +47,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -690,6 +695,20 @@ def timed_steps(models, imgs, args, dev, n):
     return time.perf_counter() - t0, out
 
 
+DUMP_MAX_VALUES = 1 << 22          # per output: 16 MiB of float32; a larger output is dumped as a fixed, seeded sample
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy, float32, for each output.  An output of more than DUMP_MAX_VALUES values is written as its values at a
+    seeded sample of flat indices that depends on its size alone, so that two builds can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32)
+        if a.size > DUMP_MAX_VALUES:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -709,7 +728,7 @@ def main():
     ap.add_argument('--extras', action='store_true',
                     help='also run the secondary legs: pcie_inclusive, the A/B legs (row_major_raster, patch_lanes_unbatched, '
                          'full_patch_tensors), cli_inclusive and a CPU baseline per config (minutes)')
-    ap.add_argument('--no-extras', action='store_true', help='also skip exact_fp32 (the only secondary leg of a default run)')
+    ap.add_argument('--no-extras', action='store_true', help='also skip exact_fp32 (the only secondary leg of a --full run)')
     ap.add_argument('--no-configs', action='store_true', help='skip the per-config legs (BASELINE configs 2, 3, 5 one by one)')
     ap.add_argument('--exact-steps', type=int, default=2)
     ap.add_argument('--dry-run', action='store_true', help='CPU-only plumbing check over gloo (no hot path, not a measurement)')
@@ -717,7 +736,14 @@ def main():
                     help="weak (default): every rank times --steps micrographs; strong: BASELINE config 4's FIXED job of --images "
                          'micrographs is dealt i = rank (mod N) to the ranks (--steps is then ignored)')
     ap.add_argument('--images', type=int, default=256, help='--scaling strong: micrographs of the whole job')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure after the timed steps: kernel timing and '
+                         'roofline, energy, exact_fp32, the per-config legs, cpu_baseline and parity (the options above that '
+                         'select or skip these legs apply only here; --extras implies --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write rank 0's outputs of the last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    args.full = args.full or args.extras
 
     from topaz_amd import parallel
     if args.gpus > 1 and not parallel.under_launcher():
@@ -751,8 +777,11 @@ def main():
     # share cycles through a bounded set of resident micrographs
     n_res = min(args.steps, 8) if args.scaling == 'strong' else args.steps
     n_img = n_res + args.warmup
-    host_imgs = [np.random.RandomState(1000 + rank + i * world).randn(args.size, args.size).astype(np.float32)
-                 for i in range(n_img)]
+    def micrograph(i):
+        return np.random.RandomState(1000 + rank + i * world).randn(args.size, args.size).astype(np.float32)
+    # (one RandomState per micrograph: generated on torch's host threads, the arrays are those of a serial loop)
+    with ThreadPoolExecutor(max(1, torch.get_num_threads())) as ex:
+        host_imgs = list(ex.map(micrograph, range(n_img)))
     imgs = [torch.from_numpy(h).to(dev) for h in host_imgs]
     models = build_models(args.workload)
     warm_picks = [run_step(models, imgs[n_res + w], args) for w in range(args.warmup)]
@@ -763,7 +792,7 @@ def main():
         parallel.gather_pick_tables([rank + i * world for i in range(len(warm_picks))], [p[0] for p in warm_picks],
                                     [p[1] for p in warm_picks], cdev)
     del warm_picks
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # roofline evidence: HIP events around the convolution launches of the TIMED steps (those of >= 20 GFLOP: ~170 of
         # ~700 launches per step, > 95 % of the kernel time), recorded on the stream the kernels are launched on and
         # resolved only after the timed region; costs < 0.5 % of the step
@@ -775,7 +804,8 @@ def main():
     parallel.barrier(cdev)
     launches0 = ctx.launches()
     sampler = GpuSampler(gpu)
-    sampler.__enter__()                                  # (joined after the timed region: its 25 ms sleep is not part of the job)
+    if args.full:
+        sampler.__enter__()                              # (joined after the timed region: its 25 ms sleep is not part of the job)
     t0 = time.perf_counter()
     cpu0 = time.process_time()                           # host CPU seconds of this rank process (all its threads)
     step_t, mem_used = [], {}
@@ -819,7 +849,97 @@ def main():
     dt = parallel.max_over_ranks(dt, cdev)
     t_gather = parallel.max_over_ranks(t_gather, cdev)
     n_picks = int(sum(int(s.numel()) for s in scs)) if have_picks else 0
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the pick table, or the denoised micrograph
+        dump_outputs(args.dump_outputs, {'pick_scores': scs[-1], 'pick_coords': cds[-1]} if have_picks else {'denoised': scs[-1]})
 
+    # images the 2xf16 path sent back to the fp32 kernels (an activation beyond the f16 range): 0 on this workload
+    fp32_reruns = 0
+    for key in ('denoise', 'score'):
+        if key in models:
+            dm = models[key][0].model.device_model if key == 'denoise' else models[key][0].device_model
+            fp32_reruns += int(dm.split_stats()[2])
+    configs, leg_s = None, {}
+    if args.full:
+        report, configs, leg_s = full_report(args, ctx, models, imgs, host_imgs, dev, gpu, rank, world, dt, sampler)
+
+    if rank == 0:
+        out = {
+            'metric': 'micrographs/sec (4096x4096 fp32) denoise+score, NMS parity',
+            'value': total_steps / dt,
+            'unit': 'micrographs/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': 1e3 * dt / max(1, args.steps),
+            'higher_is_better': True,
+            'scaling': args.scaling,
+            'rccl_world': rccl_world,
+            'host_placement': {'rank0_cpus': len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else None,
+                               'pinned_to_gpu_numa_node': bool(os.environ.get('TOPAZ_AMD_RANK_CPUS')),
+                               'host_cpus_before_pinning': len(_ORIG_AFFINITY) if _ORIG_AFFINITY is not None else None},
+            'rank_ms_per_step': {'min': min(rank_ms), 'max': max(rank_ms), 'all': [round(v, 3) for v in rank_ms]},
+            # host CPU time each rank process spent per step (launch thread, runtime, Python): what 8 ranks on one host add up to
+            'rank_host_cpu_ms_per_step': {'max': max(rank_cpu_ms), 'all': [round(v, 3) for v in rank_cpu_ms]},
+            'vs_baseline': None,
+            'dtype': 'f32 (convs: fp32 operands carried as two f16 halves on the f16 MFMA, three exact products per '
+                     'multiply-add accumulated in f32 -- fp32-level error, fp32-MFMA re-run on f16-range overflow; '
+                     'NMS in fp32; the exact-fp32-multiply rate is reported as exact_fp32)',
+            'data': 'synthetic (N(0,1) micrographs seed 1000+i; seeded random weights of the named architectures)',
+            'config': {
+                'workload': {'pipeline': 'denoise(unet b11/t5 nf48, -s 1024 -p 500) -> score(resnet8 u64, filled) -> NMS(r=14,t=-6)',
+                             'extract': 'score(resnet8 u64, filled) -> NMS(r=14,t=-6)',
+                             'denoise': 'denoise(unet b11/t5 nf48, -s 1024 -p 500)'}[args.workload],
+                'image': f'{args.size}x{args.size} fp32', 'images_per_rank': args.steps, 'images_total': total_steps,
+                'parallelism': f'one micrograph per rank x{world}; RCCL gather of pick tables',
+                'picks_per_image': n_picks / max(1, len(scs)) if have_picks else None,
+                'patch_windows': 'on: a denoise patch computes, layer by layer, only what its kept 1024^2 centre depends on '
+                                 '(bit-identical to computing the 2024^2 tensors in full; full_patch_tensors = the A/B leg)',
+            },
+            'gather_ms': 1e3 * t_gather,
+            'launches_per_step': launches_per_step,
+            'fp32_reruns': fp32_reruns,
+        }
+        if args.full:
+            out.update(report)
+        if step_t:
+            n = len(step_t)
+            w = min(32, n // 2) or 1
+            d_ms = [1e3 * (b - a) for a, b in zip([t0] + step_t[:-1], step_t)]
+            ks = sorted(mem_used)
+            out['soak'] = {
+                'images': n, 'first_ms_per_step': sum(d_ms[:w]) / w, 'last_ms_per_step': sum(d_ms[-w:]) / w, 'window': w,
+                'slowest_step_ms': max(d_ms), 'fastest_step_ms': min(d_ms),
+                'device_bytes_in_use_after_step': {str(k + 1): int(mem_used[k]) for k in ks},
+                'pool_growth_bytes_after_warm_up': int(mem_used[ks[-1]] - mem_used[ks[0]]) if len(ks) >= 2 else 0,
+                'peak_device_gb': max(mem_used.values()) / 1e9 if mem_used else None,
+                'fp32_reruns': fp32_reruns,
+                'what': f'--scaling strong: the fixed job of {args.images} micrographs ({n} on this rank, cycling through '
+                        f'{n_res} resident inputs) through denoise -> score -> NMS; per-step host clock (each step ends with the '
+                        'host read of its pick count), device memory from hipMemGetInfo'}
+        if configs is not None:
+            out['configs'] = configs
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            t_leg = time.perf_counter()
+            keep = {}
+            out['cpu_baseline'] = cpu_baseline(models, args, keep)
+            leg_s['cpu_baseline'] = time.perf_counter() - t_leg
+            # the same arrays through the HIP path: parity as part of the line (and of the exit status)
+            out['parity'] = parity_vs_oracle(models, keep, args, dev)
+        if args.full:
+            out['leg_seconds'] = {k: round(v, 2) for k, v in leg_s.items()}
+        print(json.dumps(out))
+        if 'parity' in out and not out['parity']['ok']:
+            sys.stderr.write(f"bench.py: PARITY FAILED against the oracle: {out['parity']}\n")
+            sys.exit(3)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def full_report(args, ctx, models, imgs, host_imgs, dev, gpu, rank, world, dt, sampler):
+    """What `--full` measures after the timed region: the roofline from the HIP events of the timed steps (and from extra
+    steps), the sustained-MFMA probe and the energy view, exact_fp32, the --extras legs and the per-config legs.
+    Returns (line fields, configs or None, seconds per leg)."""
     # ---- roofline: per-kernel HIP-event times of the launches of the timed steps, per step
     merged, other, conv_ms, conv_n, conv_flops = {}, {'conv_direct_ms': 0.0, 'elementwise_ms': 0.0, 'nms_ms': 0.0}, 0.0, 0, 0.0
     n_prof_steps = args.steps
@@ -939,9 +1059,9 @@ def main():
             ctx.set_lanes(True)
         hbm_rows.sort(key=lambda r: -r['ms'])
 
-    # ---- extra legs (after the timed region, N = 1 only).  A default run keeps exact_fp32 (the exact-fp32-multiply twin of
+    # ---- extra legs (after the timed region, N = 1 only).  A --full run keeps exact_fp32 (the exact-fp32-multiply twin of
     # `value`); everything else -- host-resident input, the A/B legs, the CLI from files, a CPU baseline per config -- is behind
-    # --extras, so that the driver's run stays well inside a minute
+    # --extras, so that a --full run stays well inside a minute
     extras = {}
     leg_s = {}
     t_leg = time.perf_counter()
@@ -1003,12 +1123,6 @@ def main():
                         'layer, only the rectangle those kept pixels depend on -- bit-identical output '
                         '(tests/test_gpu_denoise.py::test_patch_windows_are_bit_identical)'}
 
-    # images the 2xf16 path sent back to the fp32 kernels (an activation beyond the f16 range): 0 on this workload
-    fp32_reruns = 0
-    for key in ('denoise', 'score'):
-        if key in models:
-            dm = models[key][0].model.device_model if key == 'denoise' else models[key][0].device_model
-            fp32_reruns += int(dm.split_stats()[2])
     configs = None
     if rank == 0 and world == 1 and not args.no_configs and args.workload == 'pipeline':
         t_leg = time.perf_counter()
@@ -1030,103 +1144,38 @@ def main():
                 extras['cli_inclusive'] = {'error': f'{type(e).__name__}: {e}'}
             leg_s['cli_inclusive'] = time.perf_counter() - t_leg
 
-    if rank == 0:
-        out = {
-            'metric': 'micrographs/sec (4096x4096 fp32) denoise+score, NMS parity',
-            'value': total_steps / dt,
-            'unit': 'micrographs/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': 1e3 * dt / max(1, args.steps),
-            'higher_is_better': True,
-            'scaling': args.scaling,
-            'rccl_world': rccl_world,
-            'host_placement': {'rank0_cpus': len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else None,
-                               'pinned_to_gpu_numa_node': bool(os.environ.get('TOPAZ_AMD_RANK_CPUS')),
-                               'host_cpus_before_pinning': len(_ORIG_AFFINITY) if _ORIG_AFFINITY is not None else None},
-            'rank_ms_per_step': {'min': min(rank_ms), 'max': max(rank_ms), 'all': [round(v, 3) for v in rank_ms]},
-            # host CPU time each rank process spent per step (launch thread, runtime, Python): what 8 ranks on one host add up to
-            'rank_host_cpu_ms_per_step': {'max': max(rank_cpu_ms), 'all': [round(v, 3) for v in rank_cpu_ms]},
-            'vs_baseline': None,
-            'dtype': 'f32 (convs: fp32 operands carried as two f16 halves on the f16 MFMA, three exact products per '
-                     'multiply-add accumulated in f32 -- fp32-level error, fp32-MFMA re-run on f16-range overflow; '
-                     'NMS in fp32; the exact-fp32-multiply rate is reported as exact_fp32)',
-            'data': 'synthetic (N(0,1) micrographs seed 1000+i; seeded random weights of the named architectures)',
-            'config': {
-                'workload': {'pipeline': 'denoise(unet b11/t5 nf48, -s 1024 -p 500) -> score(resnet8 u64, filled) -> NMS(r=14,t=-6)',
-                             'extract': 'score(resnet8 u64, filled) -> NMS(r=14,t=-6)',
-                             'denoise': 'denoise(unet b11/t5 nf48, -s 1024 -p 500)'}[args.workload],
-                'image': f'{args.size}x{args.size} fp32', 'images_per_rank': args.steps, 'images_total': total_steps,
-                'parallelism': f'one micrograph per rank x{world}; RCCL gather of pick tables',
-                'picks_per_image': n_picks / max(1, len(scs)) if have_picks else None,
-                'patch_windows': 'on: a denoise patch computes, layer by layer, only what its kept 1024^2 centre depends on '
-                                 '(bit-identical to computing the 2024^2 tensors in full; full_patch_tensors = the A/B leg)',
-            },
-            'gather_ms': 1e3 * t_gather,
-            'launches_per_step': launches_per_step,
-            'fp32_reruns': fp32_reruns,
-            'gpu_clock_power': sampler.summary(),
-            'energy': energy,
-            # the dominant kernel = the conv instantiation with the most time in a step (live HIP-event timing of the
-            # timed steps' own launches); `achieved` is algorithmic (fp32-equivalent) FLOP/s
-            'roofline': {
-                'bound': 'mfma', 'kernel': dom_name,
-                'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': traffic,
-                'traffic_detail': traffic_detail,
-                'peak_basis': ('f16 dense MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-equivalent MAC (2xf16 split)'
-                               if is_split else 'fp32 MFMA peak'),
-                'sustained_mfma': sustained,
-                'launches_per_step': dom_n, 'avg_launch_ms': dom_ms / max(1e-9, dom_n),
-                'timed_over': ('the timed steps themselves (HIP events on the launch stream)' if not args.no_kernel_timing
-                               else 'one extra step after the timed region'),
-                'algorithmic_tflop_per_launch': dom_flops / max(1e-9, dom_n) / 1e12,
-                'share_of_step': dom_ms / (1e3 * dt / args.steps) if dt > 0 else None,
-                'class_conv_mfma_fp32': cls_f32, 'class_conv_split_2xf16': cls_split,
-                'conv_kernel_ms_per_step': conv_ms, 'conv_algorithmic_tflop_per_step': conv_flops / 1e12,
-                'top_kernels': [{'kernel': k[0], 'ms': k[1], 'launches': k[2], 'tflops': k[3] / k[1] / 1e9}
-                                for k in kernels_iso[:6]],
-                'class_and_top_kernels_from': 'one extra step with the patch lanes off (kernels timed in isolation)',
-                **({} if not args.no_kernel_timing else other),
-                'hbm_bound_kernels': {'peak': HBM_PEAK_BYTES / 1e9, 'unit': 'GB/s', 'rows': hbm_rows[:6],
-                                      'from': 'one extra step, every launch timed, patch lanes off; bytes = inputs (with halo) + '
-                                              'weights read once, outputs written once'},
-                'coverage': ('convolution launches of >= 20 GFLOP (the rest, elementwise and NMS kernels are not timed inside '
-                             'the timed region)' if not args.no_kernel_timing else 'every launch of one extra step'),
-            },
-            **extras,
-        }
-        if step_t:
-            n = len(step_t)
-            w = min(32, n // 2) or 1
-            d_ms = [1e3 * (b - a) for a, b in zip([t0] + step_t[:-1], step_t)]
-            ks = sorted(mem_used)
-            out['soak'] = {
-                'images': n, 'first_ms_per_step': sum(d_ms[:w]) / w, 'last_ms_per_step': sum(d_ms[-w:]) / w, 'window': w,
-                'slowest_step_ms': max(d_ms), 'fastest_step_ms': min(d_ms),
-                'device_bytes_in_use_after_step': {str(k + 1): int(mem_used[k]) for k in ks},
-                'pool_growth_bytes_after_warm_up': int(mem_used[ks[-1]] - mem_used[ks[0]]) if len(ks) >= 2 else 0,
-                'peak_device_gb': max(mem_used.values()) / 1e9 if mem_used else None,
-                'fp32_reruns': fp32_reruns,
-                'what': f'--scaling strong: the fixed job of {args.images} micrographs ({n} on this rank, cycling through '
-                        f'{n_res} resident inputs) through denoise -> score -> NMS; per-step host clock (each step ends with the '
-                        'host read of its pick count), device memory from hipMemGetInfo'}
-        if configs is not None:
-            out['configs'] = configs
-        if world == 1 and not args.no_cpu_baseline:
-            t_leg = time.perf_counter()
-            keep = {}
-            out['cpu_baseline'] = cpu_baseline(models, args, keep)
-            leg_s['cpu_baseline'] = time.perf_counter() - t_leg
-            # the same arrays through the HIP path: parity as part of the line (and of the exit status)
-            out['parity'] = parity_vs_oracle(models, keep, args, dev)
-        out['leg_seconds'] = {k: round(v, 2) for k, v in leg_s.items()}
-        print(json.dumps(out))
-        if 'parity' in out and not out['parity']['ok']:
-            sys.stderr.write(f"bench.py: PARITY FAILED against the oracle: {out['parity']}\n")
-            sys.exit(3)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    report = {
+        'gpu_clock_power': sampler.summary(),
+        'energy': energy,
+        # the dominant kernel = the conv instantiation with the most time in a step (live HIP-event timing of the
+        # timed steps' own launches); `achieved` is algorithmic (fp32-equivalent) FLOP/s
+        'roofline': {
+            'bound': 'mfma', 'kernel': dom_name,
+            'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': traffic,
+            'traffic_detail': traffic_detail,
+            'peak_basis': ('f16 dense MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-equivalent MAC (2xf16 split)'
+                           if is_split else 'fp32 MFMA peak'),
+            'sustained_mfma': sustained,
+            'launches_per_step': dom_n, 'avg_launch_ms': dom_ms / max(1e-9, dom_n),
+            'timed_over': ('the timed steps themselves (HIP events on the launch stream)' if not args.no_kernel_timing
+                           else 'one extra step after the timed region'),
+            'algorithmic_tflop_per_launch': dom_flops / max(1e-9, dom_n) / 1e12,
+            'share_of_step': dom_ms / (1e3 * dt / args.steps) if dt > 0 else None,
+            'class_conv_mfma_fp32': cls_f32, 'class_conv_split_2xf16': cls_split,
+            'conv_kernel_ms_per_step': conv_ms, 'conv_algorithmic_tflop_per_step': conv_flops / 1e12,
+            'top_kernels': [{'kernel': k[0], 'ms': k[1], 'launches': k[2], 'tflops': k[3] / k[1] / 1e9}
+                            for k in kernels_iso[:6]],
+            'class_and_top_kernels_from': 'one extra step with the patch lanes off (kernels timed in isolation)',
+            **({} if not args.no_kernel_timing else other),
+            'hbm_bound_kernels': {'peak': HBM_PEAK_BYTES / 1e9, 'unit': 'GB/s', 'rows': hbm_rows[:6],
+                                  'from': 'one extra step, every launch timed, patch lanes off; bytes = inputs (with halo) + '
+                                          'weights read once, outputs written once'},
+            'coverage': ('convolution launches of >= 20 GFLOP (the rest, elementwise and NMS kernels are not timed inside '
+                         'the timed region)' if not args.no_kernel_timing else 'every launch of one extra step'),
+        },
+        **extras,
+    }
+    return report, configs, leg_s
 
 
 if __name__ == '__main__':

@@ -192,6 +192,23 @@ def test_bench_weights_equal_test_weights():
             assert np.array_equal(a[k], b[k]), (arch, k)
 
 
+def test_bench_dump_outputs_float32_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: each output as <name>.npy in float32 (pick coordinates exactly); one of more than
+    DUMP_MAX_VALUES values as the same sample of its values on every call, so that two builds compare output for output;
+    a dump stays within 64 MB"""
+    import bench
+    big = np.arange(bench.DUMP_MAX_VALUES + 1024, dtype=np.float32).reshape(-1, 1024)   # distinct values: shows the indices
+    co = np.array([[1, 2], [4095, 7]], dtype=np.int32)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), {'denoised': big, 'pick_coords': co})
+    a, b = np.load(tmp_path / 'a' / 'denoised.npy'), np.load(tmp_path / 'b' / 'denoised.npy')
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_VALUES,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[-1] < big.size              # sorted flat indices, each taken once
+    c = np.load(tmp_path / 'a' / 'pick_coords.npy')
+    assert c.dtype == np.float32 and np.array_equal(c, co)
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= 64e6
+
+
 def test_unpickler_allowlist_refuses_foreign_globals(tmp_path):
     """a model file is data: globals outside the allowlist (here os.system via __reduce__) raise UnpicklingError instead
     of being called; the reference's own full-module pickles still load (tests/golden/user_model_*.sav)"""

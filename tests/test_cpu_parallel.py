@@ -268,12 +268,16 @@ def test_sum_to_root_assembles_tile_sharded_volume_world2_gloo():
     assert q.get(timeout=5) is True
 
 
-def test_rank_cpu_sets_follow_the_gpu_numa_nodes(tmp_path):
+def test_rank_cpu_sets_follow_the_gpu_numa_nodes(tmp_path, monkeypatch):
     """launch_local_ranks pins rank r to CPUs of GPU r's NUMA node (sysfs: /sys/class/drm/cardN/device/numa_node and the
     node's cpulist), GPUs of one node sharing it in equal slices; unreadable topology -> equal slices of the allowed CPUs.
     A rank really starts with that affinity."""
     import sys
-    from topaz_amd.parallel import cpu_sets_for_ranks, launch_local_ranks
+    from topaz_amd.parallel import _VISIBLE_VARS, cpu_sets_for_ranks, launch_local_ranks
+    # the card-order path needs a job without a visible-devices subset, whatever the environment this test runs in sets
+    # (the subset is checked explicitly below)
+    for v in _VISIBLE_VARS:
+        monkeypatch.delenv(v, raising=False)
     root = tmp_path / 'sys'
     for card, node in enumerate([0, 0, 1, 1]):
         d = root / 'class' / 'drm' / f'card{card}' / 'device'

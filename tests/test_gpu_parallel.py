@@ -40,7 +40,7 @@ def test_bench_under_torchrun_single_gpu(gpu_ctx):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', '29534', os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1',
-           '--size', '512', '--patch-size', '256', '--patch-padding', '64', '--no-cpu-baseline']
+           '--size', '512', '--patch-size', '256', '--patch-padding', '64', '--full', '--no-cpu-baseline']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, TOPAZ_AMD_FORCE_DIST='1'))
     assert r.returncode == 0, r.stdout + r.stderr
     import json
@@ -138,7 +138,7 @@ def test_bench_two_ranks_share_the_gpu(gpu_ctx):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, TOPAZ_AMD_SHARE_GPU='1', TOPAZ_AMD_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '1024',
-           '--patch-size', '512', '--patch-padding', '128', '--no-cpu-baseline']
+           '--patch-size', '512', '--patch-padding', '128', '--full', '--no-cpu-baseline']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -150,7 +150,7 @@ def test_bench_two_ranks_share_the_gpu(gpu_ctx):
 
 
 def test_bench_line_carries_parity_and_fails_on_a_broken_one(gpu_ctx):
-    """bench.py's own parity check: the default line carries `parity` -- the HIP path against the oracle on the
+    """bench.py's own parity check: the --full line carries `parity` -- the HIP path against the oracle on the
     arrays of the cpu_baseline leg -- and `energy`, `leg_seconds`; the process exits 0 only when the bars hold.  The failing side is
     checked on the function itself: a tampered oracle array makes `ok` false (bench.py then exits 3)."""
     import argparse
@@ -158,7 +158,7 @@ def test_bench_line_carries_parity_and_fails_on_a_broken_one(gpu_ctx):
     import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '1', '--warmup', '1', '--size', '768', '--patch-size', '384',
-           '--patch-padding', '96', '--cpu-sample', '512', '--cpu-score-sample', '512', '--no-configs']
+           '--patch-padding', '96', '--cpu-sample', '512', '--cpu-score-sample', '512', '--full', '--no-configs']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -182,3 +182,32 @@ def test_bench_line_carries_parity_and_fails_on_a_broken_one(gpu_ctx):
     bad = dict(keep, logit=logit + np.float32(3e-4))
     out = bench.parity_vs_oracle(models, bad, args, torch.device('cuda', 0))
     assert not out['ok'] and out['logit_max_abs'] > 1e-4
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(gpu_ctx, tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline line alone, nothing measured after the
+    timed region; --dump-outputs writes the pick table of its last timed step, which the same scorer on the same seeded
+    micrograph (seed 1000 + 2 for the third step) reproduces in this process"""
+    import json
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / 'out'
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--workload', 'extract', '--size', '512',
+           '--dump-outputs', str(d)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 3 and line['config']['images_total'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['unit'] == 'micrographs/s' and line['higher_is_better'] is True and line['metric'] and line['dtype']
+    for k in ('roofline', 'energy', 'gpu_clock_power', 'exact_fp32', 'configs', 'cpu_baseline', 'parity', 'leg_seconds'):
+        assert k not in line, k
+    sc, co = np.load(d / 'pick_scores.npy'), np.load(d / 'pick_coords.npy')
+    assert sc.dtype == np.float32 and co.dtype == np.float32 and co.shape == (len(sc), 2) and len(sc) > 10
+    sys.path.insert(0, root)
+    import bench
+    from topaz_amd import runtime as rt
+    models = bench.build_models('extract')
+    x = torch.from_numpy(np.random.RandomState(1000 + 2).randn(512, 512).astype(np.float32)).cuda()
+    s2, c2 = rt.nms(models['score'][0](x[None, None])[0, 0], 14, -6.0)
+    assert np.array_equal(sc, s2.cpu().numpy()) and np.array_equal(co, c2.cpu().numpy().astype(np.float32))
