@@ -22,6 +22,27 @@ def test_library_exports_every_declared_symbol():
     _lib.load_library()                               # prototypes attach without error
 
 
+def test_library_exports_only_the_c_abi():
+    """The dynamic symbol table holds the header's tpz_* functions and nothing else (csrc/libtopaz_hip.map): a runtime helper,
+    a kernel stub or a std:: instantiation exported from the library could interpose on a same-named symbol of the process
+    that loads it, or be interposed on."""
+    import shutil
+    import subprocess
+    from topaz_amd import _lib
+    readelf = shutil.which('readelf') or shutil.which('/opt/rocm/llvm/bin/llvm-readelf')
+    if not readelf:
+        pytest.skip('neither readelf nor llvm-readelf is installed')
+    header = open(os.path.join(ROOT, 'include', 'topaz_hip.h')).read()
+    declared = set(re.findall(r'\b(tpz_[a-z0-9_]+)\s*\(', header))
+    out = subprocess.run([readelf, '--dyn-syms', '-W', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set()
+    for line in out.splitlines():
+        f = line.split()              # Num: Value Size Type Bind Vis Ndx Name
+        if len(f) >= 8 and f[0].endswith(':') and f[4] in ('GLOBAL', 'WEAK') and f[6] != 'UND':
+            exported.add(f[7].split('@')[0])
+    assert declared and exported - {'_init', '_fini'} == declared, sorted(exported ^ declared)[:20]
+
+
 def test_stray_debug_variables_change_nothing_without_TPZ_DEBUG(monkeypatch):
     """The library's A/B switches (TPZ_EXACT_FP32, TPZ_NO_ROI, ...) are read by ONE function and only under TPZ_DEBUG=1
     (VERDICT r05 item 7): a variable left in a user's environment must not change the arithmetic or the schedule of a job."""

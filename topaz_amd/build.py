@@ -4,7 +4,8 @@
 
 One object per .hip translation unit (compiled in parallel, rebuilt only when the content of the
 source, of a header it includes or the flags changed), linked into topaz_amd/libtopaz_hip.so.  hipcc cross-compiles for gfx950
-without a GPU, so this runs on the CPU-only build container as well as on the MI355X box.
+without a GPU, so this runs on the CPU-only build container as well as on the MI355X box.  The link applies the version script
+csrc/libtopaz_hip.map: the library exports the tpz_* functions of include/topaz_hip.h and nothing else.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 BUILD = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libtopaz_hip.so')
+MAP = os.path.join(CSRC, 'libtopaz_hip.map')
 ARCH = 'gfx950'
 
 
@@ -35,6 +37,15 @@ def _sources():
 
 
 FLAGS = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
+
+
+def _default_jobs() -> int:
+    """Compile workers: MAX_JOBS, else CMAKE_BUILD_PARALLEL_LEVEL, else the CPU count; at most 16."""
+    for var in ('MAX_JOBS', 'CMAKE_BUILD_PARALLEL_LEVEL'):
+        v = os.environ.get(var, '').strip()
+        if v.isdigit() and int(v) > 0:
+            return min(int(v), 16)
+    return min(os.cpu_count() or 4, 16)
 
 
 def _all_headers():
@@ -86,13 +97,13 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = True) ->
     if todo:
         if verbose:
             print(f'[topaz_amd.build] compiling {len(todo)} translation unit(s) for {ARCH}', file=sys.stderr)
-        jobs = jobs or min(len(todo), os.cpu_count() or 4)
+        jobs = jobs or min(len(todo), _default_jobs())
         with ThreadPoolExecutor(max_workers=jobs) as ex:
             list(ex.map(lambda so: _compile(hipcc, *so), todo))
     link_mark = os.path.join(BUILD, 'link.sha1')
-    link_fp = hashlib.sha1(''.join(open(o[:-2] + '.sha1').read() for o in objs).encode()).hexdigest()
+    link_fp = hashlib.sha1((''.join(open(o[:-2] + '.sha1').read() for o in objs) + open(MAP).read()).encode()).hexdigest()
     if todo or not os.path.exists(LIB) or not os.path.exists(link_mark) or open(link_mark).read().strip() != link_fp:
-        cmd = [hipcc, f'--offload-arch={ARCH}', '-shared', '-fPIC', '-o', LIB] + objs
+        cmd = [hipcc, f'--offload-arch={ARCH}', '-shared', '-fPIC', f'-Wl,--version-script={MAP}', '-o', LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stdout}\n{r.stderr}')

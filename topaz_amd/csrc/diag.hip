@@ -32,9 +32,14 @@ __global__ __launch_bounds__(256) void mfma_spin_kernel(const spin_half8* __rest
     if (t == 0) { ticks[0] = c1 - c0; ticks[1] = w1 - w0; }
 }
 
+namespace rt {
+
+// (declared in rt_internal.h: tpz_prof_mfma_sustained is its one caller)
 hipError_t launch_mfma_spin(const void* src, float* out, int n_wg, int iters, unsigned long long* ticks, hipStream_t st) {
     hipLaunchKernelGGL(mfma_spin_kernel, dim3(n_wg), dim3(256), 0, st, (const spin_half8*)src, out, iters, ticks);
     return hipGetLastError();
 }
+
+}  // namespace rt
 
 }  // namespace tpz

@@ -6,19 +6,21 @@
 // kernel registry
 // ------------------------------------------------------------------------------------------------
 namespace tpz {
-static std::vector<ConvKernelInfo>& registry() {
+namespace {
+std::vector<ConvKernelInfo>& registry() {
     static std::vector<ConvKernelInfo> r;
     return r;
 }
+std::vector<SplitKernelInfo>& split_registry() {
+    static std::vector<SplitKernelInfo> r;
+    return r;
+}
+}  // namespace
 void register_conv(const ConvKernelInfo& info) { registry().push_back(info); }
 const ConvKernelInfo* find_conv(int dims, int K, int D, int MT, bool cin1, int epi) {
     for (const auto& k : registry())
         if (k.dims == dims && k.K == K && k.D == D && k.MT == MT && k.cin1 == (cin1 ? 1 : 0) && k.epi == epi) return &k;
     return nullptr;
-}
-static std::vector<SplitKernelInfo>& split_registry() {
-    static std::vector<SplitKernelInfo> r;
-    return r;
 }
 void register_split(const SplitKernelInfo& info) { split_registry().push_back(info); }
 const SplitKernelInfo* find_split(int K, int D, int MT, int epi, int KX, int sps) {
@@ -36,7 +38,10 @@ const SplitKernelInfo* find_split(int K, int D, int MT, int epi, int KX, int sps
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-static std::string g_last_error;
+namespace tpz::rt {
+namespace {
+std::string g_last_error;
+}  // namespace
 const std::string& last_global_error() { return g_last_error; }
 void restore_errors(tpz_ctx* ctx, const std::string& ctx_err, const std::string& global_err) {
     if (ctx) ctx->err = ctx_err;
@@ -334,7 +339,10 @@ int rec_flush(tpz_ctx* ctx) {
     return rc;
 }
 
-extern "C" {
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
 
 int tpz_debug_switches(char* buf, int buf_len) {
     const DebugEnv d = debug_env();
@@ -628,5 +636,3 @@ int tpz_prof_get(tpz_ctx* ctx, int cls, double* ms, long long* launches, double*
     if (flops) *flops = ctx->acc_flops[cls];
     return 0;
 }
-
-}  // extern "C"

@@ -1,7 +1,9 @@
 // Denoising drivers: Denoise._denoise on a region, the patched 2-D pass and the tiled 3-D pass (batched over the lanes).
 #include "rt_internal.h"
 
-extern "C" {
+namespace tpz::rt {
+namespace {
+
 // ---- denoising ---------------------------------------------------------------------------------
 // Denoise._denoise on a (strided) region: mean / unbiased std -> normalise -> network -> un-normalise.
 // mode 1: plain; mode 2: the un-normalisation also applies the volume's std*y+mu with g = {mu, std}.
@@ -10,7 +12,7 @@ extern "C" {
 // micrograph -- nothing on 288 GB -- but a 384^3 tile is 8x that.  The batch is cut to what fits 90 % of the free device memory
 // (+ what the pools already hold), counting for one image every tensor the program allocates (no reuse: an upper bound);
 // below 2 the pass falls back to single patches on the lanes.
-static int batch_that_fits(tpz_ctx* ctx, const tpz_model* m, int D, int H, int W) {
+int batch_that_fits(tpz_ctx* ctx, const tpz_model* m, int D, int H, int W) {
     if (ctx->batch < 2) return ctx->batch;
     struct S { int C, D, H, W; };
     std::vector<S> s(m->n_slots, S{0, 0, 0, 0});
@@ -48,8 +50,8 @@ static int batch_that_fits(tpz_ctx* ctx, const tpz_model* m, int D, int H, int W
     return fit >= 2 ? fit : 0;
 }
 
-static int denoise_region(tpz_model* m, const Slot& view, float* d_out_dense, int mode = 1,
-                          const float* d_g = nullptr, bool split = false, const Rect* keep = nullptr) {
+int denoise_region(tpz_model* m, const Slot& view, float* d_out_dense, int mode = 1,
+                   const float* d_g = nullptr, bool split = false, const Rect* keep = nullptr) {
     tpz_ctx* ctx = m->ctx;
     float* nrm = next_nrm(ctx);
     const float* vp_ = view.p;
@@ -73,7 +75,7 @@ static int denoise_region(tpz_model* m, const Slot& view, float* d_out_dense, in
     return rc;
 }
 
-static int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int patch, int pad, float* d_out, bool split) {
+int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int patch, int pad, float* d_out, bool split) {
     tpz_ctx* ctx = m->ctx;
     const int s = patch + pad;
     const bool use_patch = patch > 0 && (s < H || s < W);     // denoise.py:329-330
@@ -137,27 +139,8 @@ static int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int pa
     return rc_all;
 }
 
-int tpz_denoise_2d(tpz_model* m, const float* d_in, int H, int W, int patch, int pad, float* d_out) {
-    if (!m || !d_in || !d_out) return fail(m ? m->ctx : nullptr, "tpz_denoise_2d: NULL argument");
-    tpz_ctx* ctx = m->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int Do, Ho, Wo;
-    tpz_model_out_shape(m, 1, 8 * 64, 8 * 64, &Do, &Ho, &Wo);
-    if (Ho != 8 * 64 || Wo != 8 * 64) return fail(ctx, "tpz_denoise_2d: the model does not preserve the image size");
-    if (m->split_ok && !ctx->exact) {
-        // 2xf16 path for the whole micrograph; any activation beyond the f16 range re-runs it on the fp32 kernels
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream));
-        if (denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, true)) return 1;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (*ctx->h_flag == 0) { ++m->n_split; return 0; }
-        ++m->n_fallback;
-    }
-    return denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, false);
-}
-
-static int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int patch, int pad, float* d_out,
-                           bool split, int shard = 0, int n_shards = 1) {
+int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int patch, int pad, float* d_out,
+                    bool split, int shard = 0, int n_shards = 1) {
     tpz_ctx* ctx = m->ctx;
     if (patch < 1) {
         Slot v;
@@ -244,6 +227,32 @@ static int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W,
     return rc;
 }
 
+}  // namespace
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
+
+int tpz_denoise_2d(tpz_model* m, const float* d_in, int H, int W, int patch, int pad, float* d_out) {
+    if (!m || !d_in || !d_out) return fail(m ? m->ctx : nullptr, "tpz_denoise_2d: NULL argument");
+    tpz_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int Do, Ho, Wo;
+    tpz_model_out_shape(m, 1, 8 * 64, 8 * 64, &Do, &Ho, &Wo);
+    if (Ho != 8 * 64 || Wo != 8 * 64) return fail(ctx, "tpz_denoise_2d: the model does not preserve the image size");
+    if (m->split_ok && !ctx->exact) {
+        // 2xf16 path for the whole micrograph; any activation beyond the f16 range re-runs it on the fp32 kernels
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream));
+        if (denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, true)) return 1;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (*ctx->h_flag == 0) { ++m->n_split; return 0; }
+        ++m->n_fallback;
+    }
+    return denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, false);
+}
+
 int tpz_denoise_3d_shard(tpz_model* m, const float* d_in, int D, int H, int W, int patch, int pad, int shard, int n_shards,
                          float* d_out) {
     if (!m || !d_in || !d_out) return fail(m ? m->ctx : nullptr, "tpz_denoise_3d: NULL argument");
@@ -265,5 +274,3 @@ int tpz_denoise_3d_shard(tpz_model* m, const float* d_in, int D, int H, int W, i
 int tpz_denoise_3d(tpz_model* m, const float* d_in, int D, int H, int W, int patch, int pad, float* d_out) {
     return tpz_denoise_3d_shard(m, d_in, D, H, W, patch, pad, 0, 1, d_out);
 }
-
-}  // extern "C"

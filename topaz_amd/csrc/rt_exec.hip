@@ -4,8 +4,11 @@
 // ------------------------------------------------------------------------------------------------
 // executor
 // ------------------------------------------------------------------------------------------------
+namespace tpz::rt {
+namespace {
+
 // grid, XCD swizzle and phase stagger of one conv_mfma launch; a.Dout/Hout/Wout, n_chunks, cog_inner are set
-static int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int n_cog, double flops) {
+int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int n_cog, double flops) {
     a.xcd_swizzle = 1;
     if (a.wy1 <= 0) { a.wy0 = a.wx0 = 0; a.wy1 = a.Hout; a.wx1 = a.Wout; }      // no window: the whole lattice
     else flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
@@ -36,7 +39,7 @@ static int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int 
 // launch window of an fp32 kernel from the part of the layer's tensor that is needed (`scale` = 2: the half-resolution lattice of
 // a per-parity launch).  The left edge is rounded down to a multiple of 4 pixels: the 16-byte granules of the MFMA kernels'
 // loader stay aligned; the few extra columns are computed like any others.
-static void set_window(ConvArgs& a, const Rect& need, int scale = 1) {
+void set_window(ConvArgs& a, const Rect& need, int scale = 1) {
     if (!need.on) return;
     a.wy0 = need.y0 / scale; a.wx0 = (need.x0 / scale) & ~3;
     a.wy1 = std::min(a.Hout, (need.y1 + scale - 1) / scale);
@@ -50,8 +53,8 @@ static void set_window(ConvArgs& a, const Rect& need, int scale = 1) {
 
 // conv(cat(upsample2x(s1), s2)) by output parity (prepare_phases): 2^dims plain launches over s1 that write the
 // strided output positions, then the skip-source launch over the full grid that adds itself in place.
-static int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const Slot& s1, const Slot& s2,
-                           Slot& dst) {
+int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const Slot& s1, const Slot& s2,
+                    Slot& dst) {
     const tpz_layer& L = rt.L;
     const LayerRT::Phase& ph = rt.phase;
     const int n_phase = 1 << L.dims;
@@ -93,12 +96,12 @@ static int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base
     return launch_mfma(ctx, *ph.ki_skip, a, ph.n_cog_skip, fl);
 }
 
-static int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops);
+int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops);
 
 // window of a launch from the part of the layer's tensor that is needed (`need` in the tensor's coordinates, `scale` = 2 for the
 // low-resolution lattice of a per-parity / sub-pixel launch, `grow_x` extra columns at the right: the column kernel of a last
 // conv); flops are scaled by the fraction of the lattice that is computed
-static void set_window(SplitArgs& a, const Rect& need, int scale = 1, int grow_x = 0) {
+void set_window(SplitArgs& a, const Rect& need, int scale = 1, int grow_x = 0) {
     if (!need.on) return;
     a.wy0 = need.y0 / scale; a.wx0 = need.x0 / scale;
     a.wy1 = std::min(a.Hout, (need.y1 + scale - 1) / scale);
@@ -115,7 +118,7 @@ static void set_window(SplitArgs& a, const Rect& need, int scale = 1, int grow_x
 
 // the weights-resident kernel (conv_rw.h) for a 3x3 32 -> 32 layer: window and tile grid as launch_split, one persistent
 // workgroup per CU
-static int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops) {
+int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops) {
     static char names[3][3][96];
     const int di = dil == 1 ? 0 : dil == 2 ? 1 : 2;
     if (!names[di][epi][0])
@@ -145,6 +148,8 @@ static int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops)
     if (e != hipSuccess) return fail(ctx, "conv_rw launch failed: %s", hipGetErrorString(e));
     return 0;
 }
+
+}  // namespace
 
 // one conv layer on the 2xf16 path: split source (and residual), split output or fused fp32 head
 // (fold: the input of a folded 1x1 projection, split cells -- the layer then runs ks_fold with the projection's channels
@@ -220,9 +225,11 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
     return launch_split(ctx, ks, a, rt.s_n_cog, flops);
 }
 
+namespace {
+
 // the K-loop schedule of this launch (SplitArgs::plan): tile-invariant, so one table per (kernel, cells, sources) serves every
 // launch of the layer; the first launch builds and uploads it (a blocking copy, once)
-static const SplitStep* split_plan(tpz_ctx* ctx, const SplitKernelInfo& ks, const SplitArgs& a, bool* next_ok) {
+const SplitStep* split_plan(tpz_ctx* ctx, const SplitKernelInfo& ks, const SplitArgs& a, bool* next_ok) {
     SplitPlanKey k;
     memset(&k, 0, sizeof k);
     k.cells_in = a.cells_in; k.cells_in1 = a.cells_in1; k.n_chunks = a.n_chunks; k.has_in2 = a.in2 != nullptr;
@@ -240,7 +247,7 @@ static const SplitStep* split_plan(tpz_ctx* ctx, const SplitKernelInfo& ks, cons
     return d;
 }
 
-static int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops) {
+int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops) {
     if (a.wy1 < 0) {
         a.wy1 = -a.wy1;
         flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
@@ -329,7 +336,7 @@ static int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, i
 
 // conv(cat(upsample2x(s1), s2)) on the 2xf16 path (prepare_split_phases).  s1: split; s2: fp32 when it is the
 // 1-channel image (stem kernel), else split; dst: split.
-static int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot& s2, Slot& dst) {
+int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot& s2, Slot& dst) {
     const tpz_layer& L = rt.L;
     const LayerRT::SplitPhase& sp = rt.sphase;
     const LayerRT::Phase& ph = rt.phase;
@@ -482,7 +489,7 @@ static int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1
 }
 
 // 1-channel stem on the 2xf16 path: x-shifted copy of the image (kx taps as channels), then a k x 1 column kernel
-static int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, bool pooled = false) {
+int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, bool pooled = false) {
     const tpz_layer& L = rt.L;
     const SplitKernelInfo& ks = pooled ? *rt.ks_pool : *rt.ks_stem;
     if (s1.pitch != s1.W || s1.ps != (long long)s1.H * s1.W) return fail(ctx, "2xf16 stem needs a dense input");
@@ -535,8 +542,8 @@ static int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot&
 
 // 1-output-channel last conv on the 2xf16 path: k virtual output channels (one per kx tap) over W + 2*pad columns
 // by a k x 1 column kernel storing fp32, then out[x] = sum_v Y[v][x + v] + bias (and the un-normalisation)
-static int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, const float* d_nrm, int norm_out,
-                          const Slot* sres = nullptr) {
+int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, const float* d_nrm, int norm_out,
+                   const Slot* sres = nullptr) {
     const tpz_layer& L = rt.L;
     if (rt.d_wlast) {
         // one pass: stencil + bias + residual + un-normalisation (conv_cout1_split_kernel)
@@ -612,7 +619,7 @@ static int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot&
 }
 
 // the slot's 2-D tensor in the wanted format: the producer's own buffer, or a converted copy made once
-static float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
+float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
     if (s.split == want_split) return s.p;
     if (s.alt) return s.alt;
     if (s.pitch != s.W || s.ps != (long long)s.H * s.W || s.cs != s.ps * s.D) return nullptr;
@@ -633,8 +640,8 @@ static float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
     return q;
 }
 
-static int run_conv(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* s2, const Slot* sres, Slot& dst,
-                    const float* d_nrm, int norm_out, bool split_out = false) {
+int run_conv(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* s2, const Slot* sres, Slot& dst,
+             const float* d_nrm, int norm_out, bool split_out = false) {
     const tpz_layer& L = rt.L;
     ConvArgs a;
     memset(&a, 0, sizeof a);
@@ -698,7 +705,7 @@ static int run_conv(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot*
 // layer is written to d_out (dense).  d_nrm != nullptr: slot 0 is normalised on load wherever it is read
 // and the output is un-normalised (Denoise._denoise, topaz/denoise.py:283-295).
 // PyTorch 'nearest' source index exactly as the kernels compute it (conv_mfma.h nearest_src)
-static int nearest_src_host(int dst, int in_sz, int out_sz) {
+int nearest_src_host(int dst, int in_sz, int out_sz) {
     if (in_sz == out_sz) return dst;
     const float scale = (float)in_sz / (float)out_sz;
     const int v = (int)floorf((float)dst * scale);
@@ -719,7 +726,7 @@ static int nearest_src_host(int dst, int in_sz, int out_sz) {
 // kernels only: the plane-stacked launches take the planes of the box (SplitArgs::wz0, Dout) besides its rectangle.
 // Returns an empty vector when the program cannot be windowed (a 3-D program on the fp32 kernels, a 2xf16 program with a layer
 // left on an fp32 kernel, an op it does not know).
-static std::vector<Rect> need_regions(const tpz_model* m, int D0, int H0, int W0, const Rect& keep, bool split) {
+std::vector<Rect> need_regions(const tpz_model* m, int D0, int H0, int W0, const Rect& keep, bool split) {
     const int nl = (int)m->layers.size();
     std::vector<Rect> need;
     // (TPZ_TRACE_HOST=1 says which check left a program whole)
@@ -828,6 +835,8 @@ static std::vector<Rect> need_regions(const tpz_model* m, int D0, int H0, int W0
         }
     return need;
 }
+
+}  // namespace
 
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split, const Rect* keep) {
     tpz_ctx* ctx = m->ctx;
@@ -998,3 +1007,4 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
     return rc;
 }
 
+}  // namespace tpz::rt

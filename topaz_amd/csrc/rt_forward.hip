@@ -1,8 +1,13 @@
 // Scoring drivers (tpz_model_forward: range-scaled pass, internal tiling) and the single-op entry points.
 #include "rt_internal.h"
 
-extern "C" {
-static bool split_volume_fits(const tpz_model* m, int D, int H, int W) {
+namespace tpz::rt {
+namespace {
+
+// The plane-stacked 3-D kernels address a whole split tensor half with 32-bit byte offsets (conv_split.h fetch): a volume whose
+// widest activation exceeds 4 GiB per half stays on the fp32 kernels.  (No tensor of these networks is larger than the input
+// in voxels: 'same' or valid convolutions, pools.)
+bool split_volume_fits(const tpz_model* m, int D, int H, int W) {
     if (D <= 1) return true;
     size_t cmax = 1;
     for (const LayerRT& rt : m->layers)
@@ -17,7 +22,7 @@ static bool split_volume_fits(const tpz_model* m, int D, int H, int W) {
 // network run on the tile grown by that halo (clipped at the image borders, where the layers' own zero padding applies as it
 // does on the whole image), minus the halo ring.  Every kept logit is computed by the same instructions on the same operands as
 // in a whole-image pass: bit-identical (tests/test_gpu_scoring.py::test_internal_tiling_is_bit_identical).
-static int model_halo(const tpz_model* m) {
+int model_halo(const tpz_model* m) {
     int h = 0;
     for (const LayerRT& rt : m->layers) {
         const tpz_layer& L = rt.L;
@@ -28,7 +33,7 @@ static int model_halo(const tpz_model* m) {
     return (h + 1) & ~1;
 }
 
-static int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, int Do, int Ho, int Wo, bool split) {
+int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, int Do, int Ho, int Wo, bool split) {
     tpz_ctx* ctx = m->ctx;
     const int halo = (D == 1 && Ho == H && Wo == W) ? model_halo(m) : -1;
     if (halo < 0 || (long long)H * W <= ctx->tile_limit_px) {
@@ -69,6 +74,13 @@ static int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, in
         }
     return 0;
 }
+
+}  // namespace
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
 
 int tpz_model_forward(tpz_model* m, const float* d_in, int n, int D, int H, int W, float* d_out) {
     if (!m || !d_in || !d_out) return fail(m ? m->ctx : nullptr, "tpz_model_forward: NULL argument");
@@ -260,5 +272,3 @@ int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_
     return tpz_conv(ctx, 2, d_in, 1, 1, H, W, nullptr, 1, 1, H, W, h_w, &bias, 1, k, 1, k / 2, 1.0f, nullptr, 0, nullptr,
                     nullptr, nullptr, 0.f, d_out);
 }
-
-}  // extern "C"

@@ -1,4 +1,7 @@
-// Internal declarations of the libtopaz_hip.so runtime (NOT part of the C-ABI: include/topaz_hip.h is).
+// Internal declarations of the libtopaz_hip.so runtime (NOT part of the C-ABI: include/topaz_hip.h is).  Everything here lives in
+// namespace tpz::rt but the structs behind the C header's opaque handles (tpz_ctx, tpz_model), which the header declares at
+// global scope.  The library exports the tpz_* functions only (libtopaz_hip.map); each runtime file keeps its own helpers in an
+// anonymous namespace, defines the helpers other files share in tpz::rt and its tpz_* entry points last, at global scope.
 // The runtime is split into translation units by concern:
 //   rt_core.hip     kernel registries, the context (streams, workspace pools, patch lanes, the batched-launch recorder, the
 //                   HIP-event profiler), its setters, the debug switches
@@ -28,7 +31,7 @@
 #include "conv_rw.h"
 #include "kernels_misc.h"
 
-using namespace tpz;
+namespace tpz::rt {
 
 // ---- debug / A-B switches ----------------------------------------------------------------------------------------------
 // Every switch below changes how a job computes or is scheduled.  They exist for tools/ and tests/ (same-process A/B legs,
@@ -91,9 +94,11 @@ struct RecOp {
     const void* key = nullptr;
 };
 
+}  // namespace tpz::rt
+
 struct tpz_ctx {
     int device = 0;
-    DebugEnv dbg;                 // the debug switches as they stood when the ctx was created (all off without TPZ_DEBUG=1)
+    tpz::rt::DebugEnv dbg;        // the debug switches as they stood when the ctx was created (all off without TPZ_DEBUG=1)
     int n_cus = 256;              // compute units (persistent grids are sized from it)
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -115,7 +120,7 @@ struct tpz_ctx {
         std::vector<Buf> pool;
         double* d_part = nullptr;
     };
-    Lane lanes[N_LANES];
+    Lane lanes[tpz::rt::N_LANES];
     struct tpz_stage* io_stage = nullptr;     // ring behind the host-pointer entry points (created on first use)
     hipEvent_t lanes_fork = nullptr;
     hipStream_t lanes_saved_stream = nullptr;
@@ -135,7 +140,7 @@ struct tpz_ctx {
     bool rec_on = false;
     double rec_t0 = 0;                        // (TPZ_TRACE_HOST)
     int rec_cur = 0;
-    std::vector<RecOp> rec[tpz::SPLIT_MULTI_MAX];
+    std::vector<tpz::rt::RecOp> rec[tpz::SPLIT_MULTI_MAX];
     std::vector<Buf> rec_pools[TPZ_N_LANES][tpz::SPLIT_MULTI_MAX];   // per lane (two batches are in flight at a time) and image
     int rec_lane = 0;
     long long batch_mem = 0;                  // tpz_ctx_set_batch_memory: device bytes a batched pass may take (0: what is free)
@@ -162,22 +167,24 @@ struct tpz_ctx {
     // K-loop schedules of the 2xf16 kernels (conv_split.h SplitStep), built on first use per (kernel, layer shape) and kept
     // on the device for the life of the ctx: (kernel, key) -> device table
     struct SplitPlan {
-        const SplitKernelInfo* ks;
-        SplitPlanKey key;
-        SplitStep* d;
+        const tpz::SplitKernelInfo* ks;
+        tpz::SplitPlanKey key;
+        tpz::SplitStep* d;
         bool next_ok;             // holds a complete next-tile fetch: the persistent kernel may run this layer
     };
     std::vector<SplitPlan> split_plans;
     // profiling
     int prof = 0;                 // 0 off, 1 every launch, 2 conv launches of >= 20 GFLOP only (cheap enough for timed runs)
     bool prof_open = false;
-    std::vector<ProfRec> recs;
+    std::vector<tpz::rt::ProfRec> recs;
     std::vector<hipEvent_t> free_events;
-    std::vector<std::pair<const void*, ProfAcc>> per_kernel;   // conv_mfma instantiations
+    std::vector<std::pair<const void*, tpz::rt::ProfAcc>> per_kernel;   // conv_mfma instantiations
     double acc_ms[4] = {0, 0, 0, 0};
     long long acc_n[4] = {0, 0, 0, 0};
     double acc_flops[4] = {0, 0, 0, 0};
 };
+
+namespace tpz::rt {
 
 static const int PART_BLOCKS = 1024;
 static const int NRM_RING = 4096;
@@ -188,7 +195,7 @@ int fail(tpz_ctx* ctx, const char* fmt, ...);
     do {                                                                                         \
         hipError_t e__ = (expr);                                                                 \
         if (e__ != hipSuccess)                                                                   \
-            return fail(ctx, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return ::tpz::rt::fail(ctx, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
 
 // ---- rt_core.hip
@@ -302,10 +309,12 @@ struct LayerRT {
     } phase;
 };
 
+}  // namespace tpz::rt
+
 struct tpz_model {
     tpz_ctx* ctx = nullptr;
-    DebugEnv dbg;                         // the debug switches read when this model was loaded
-    std::vector<LayerRT> layers;
+    tpz::rt::DebugEnv dbg;                // the debug switches read when this model was loaded
+    std::vector<tpz::rt::LayerRT> layers;
     int n_slots = 0;
     std::vector<int> last_use;
     std::vector<void*> dev_allocs;
@@ -320,6 +329,8 @@ struct tpz_model {
     bool widened = false;                 // the program was loaded with its widths zero-padded to multiples of 16 (widen_program)
     long long n_split = 0, n_fallback = 0;
 };
+
+namespace tpz::rt {
 
 // a rectangle of a 2-D tensor (planes [z0, z1) of a 3-D one: a box); on = false: the whole tensor
 struct Rect {
@@ -374,3 +385,8 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
                    bool pooled = false, const Slot* fold = nullptr);
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split = false,
                 const Rect* keep = nullptr);
+// diag.hip: n_wg 4-wave workgroups each issue 8 * iters v_mfma_f32_16x16x32_f16 per wave on operands read from src (4096 x 16 B);
+// ticks[0] = s_memtime, ticks[1] = s_memrealtime (100 MHz) ticks of wave 0's loop
+hipError_t launch_mfma_spin(const void* src, float* out, int n_wg, int iters, unsigned long long* ticks, hipStream_t s);
+
+}  // namespace tpz::rt

@@ -1,6 +1,8 @@
 // Model loading: kernel choice per layer, weight packing, decoder phase forms, folded projections, widened programs.
 #include "rt_internal.h"
 
+namespace tpz::rt {
+
 int upload(tpz_ctx* ctx, tpz_model* m, const float* h, size_t n, float** out) {
     float* d = nullptr;
     HIPCHK(ctx, hipMalloc((void**)&d, std::max<size_t>(n, 4) * sizeof(float)));
@@ -18,10 +20,12 @@ int upload_chan(tpz_ctx* ctx, tpz_model* m, const float* h, size_t n, float** ou
     return upload(ctx, m, padded.data(), padded.size(), out);
 }
 
-static const int MT_CHOICES[] = {16, 32, 48, 64, 96, 128};
+namespace {
+
+const int MT_CHOICES[] = {16, 32, 48, 64, 96, 128};
 
 // choose the MFMA instantiation for a conv layer; returns nullptr when the direct kernel must be used
-static const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool cin1, int epi) {
+const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool cin1, int epi) {
     const ConvKernelInfo* best = nullptr;
     int best_padded = 1 << 30;
     for (int mt : MT_CHOICES) {
@@ -36,7 +40,7 @@ static const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool 
     return best;
 }
 
-static const ConvKernelInfo* choose_kernel(const tpz_layer& L) {
+const ConvKernelInfo* choose_kernel(const tpz_layer& L) {
     if (L.cout == 1 && !L.head) return nullptr;      // M = 1: nothing for the matrix cores to do
     const bool cin1 = (L.cin == 1 && L.src2 < 0);
     // epilogue variant the layer needs (conv_mfma.h EPI_*)
@@ -51,8 +55,8 @@ static const ConvKernelInfo* choose_kernel(const tpz_layer& L) {
 //   block[step][mf][k(0..3)][i(0..15)]  with lane = k*16 + i   (conv_mfma.h)
 //   generic: step = (kg*RPS + r)*K + kx, tap row = stage*RPS + r = kz*K + ky, ci = chunk*NCH + kg*4 + k
 //   CIN1:    step = r*KXG + kxg,         kx = kxg*4 + k (zero beyond K), ci = 0
-static void pack_weights(const ConvKernelInfo& ki, const float* w, int cout, int cin, int n_cog, int n_chunks,
-                         std::vector<float>& out) {
+void pack_weights(const ConvKernelInfo& ki, const float* w, int cout, int cin, int n_cog, int n_chunks,
+                  std::vector<float>& out) {
     const int K = ki.K, KZ = ki.dims == 3 ? K : 1, MW = ki.MT / 16;
     out.assign((size_t)n_cog * n_chunks * ki.W_CHUNK, 0.f);
     const size_t taps = (size_t)KZ * K * K;
@@ -94,13 +98,12 @@ static void pack_weights(const ConvKernelInfo& ki, const float* w, int cout, int
 // followed by the k-tap convolution of the skip source `b` alone, which adds itself in place and applies
 // bias + activation.  The zero padding agrees because the upsample is exact (full = 2 * low per axis);
 // run_conv() checks that at run time and otherwise keeps the fused upsample+concat loader.
-static int phase_tap(int k, int p, int ky) {
+int phase_tap(int k, int p, int ky) {
     const int v = p + ky - k / 2;                  // floor(v / 2) for negative v too
     return (v >= 0 ? v / 2 : -((-v + 1) / 2)) + phase_pad(k, p);
 }
 
-static int prepare_phases(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* w, int c1, int c2,
-                          LayerRT& rt) {
+int prepare_phases(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* w, int c1, int c2, LayerRT& rt) {
     LayerRT::Phase& ph = rt.phase;
     if (L.src2 < 0 || L.dil != 1 || (L.k != 3 && L.k != 5) || L.pad != L.k / 2 || L.res >= 0 || L.head ||
         L.post_scale_off >= 0 || c1 + c2 != L.cin || c1 < 1 || c2 < 1)
@@ -147,8 +150,8 @@ static int prepare_phases(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const 
     return 0;
 }
 
-static int prepare_layer(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* blob, size_t n_floats,
-                         LayerRT& rt, int c1 = 0, int c2 = 0) {
+int prepare_layer(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* blob, size_t n_floats, LayerRT& rt,
+                  int c1 = 0, int c2 = 0) {
     rt.L = L;
     rt.c1 = c1; rt.c2 = c2;
     if (L.op != TPZ_OP_CONV) return 0;
@@ -188,6 +191,8 @@ static int prepare_layer(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const f
     }
     return 0;
 }
+
+}  // namespace
 
 // ---- 2xf16 path (conv_split.h) ---------------------------------------------------------------------
 // weights [cout][cin][k][k] -> per (co-group, chunk, step) blocks  [plane hi|lo][m][lane = kb*16 + i][8 channels]
@@ -294,15 +299,14 @@ const SplitKernelInfo* pick_split(int k, int dil, int cout, int epi, int kx) {
     return best;
 }
 
-static thread_local std::vector<uint16_t> g_pack_tmp;
-static thread_local std::vector<float> g_inv_tmp;
+namespace {
 
 // kz_n > 1: 3-D weights [cout][cin][kz][k][k] are laid out for the plane-stacked 2-D kernel (conv_split.h): the
 // input channels of plane kz become channels [kz*cells*8, ...) of a 2-D conv with kz_n * cells * 8 input channels
 // c1_major > 0 (a multiple of 8; two-source 3-D launches, SplitArgs::vol_srcmajor): the channels [0, c1_major) of every plane
 // come first, then the remaining ones of every plane -- the order split_make_plan walks when srcmajor is set
-static int upload_split_weights(tpz_ctx* ctx, tpz_model* m, const SplitKernelInfo& ks, const float* w, int cout, int cin,
-                                int* n_cog, int* n_chunks, void** d_w, float** d_ws, int kz_n = 1, int c1_major = 0) {
+void pack_weights_split_stacked(const SplitKernelInfo& ks, const float* w, int cout, int cin, int* n_cog, int* n_chunks,
+                                std::vector<uint16_t>& packed, std::vector<float>& inv, int kz_n = 1, int c1_major = 0) {
     std::vector<float> stacked;
     if (kz_n > 1) {
         const int c8 = (int)split_cells(cin) * 8, k = ks.K;
@@ -323,14 +327,14 @@ static int upload_split_weights(tpz_ctx* ctx, tpz_model* m, const SplitKernelInf
     }
     *n_cog = (cout + ks.MT - 1) / ks.MT;
     *n_chunks = (int)((split_cells(cin) + ks.CC - 1) / ks.CC);
+    pack_weights_split(ks, w, cout, cin, *n_cog, *n_chunks, packed, inv);
+}
+
+int upload_split_weights(tpz_ctx* ctx, tpz_model* m, const SplitKernelInfo& ks, const float* w, int cout, int cin, int* n_cog,
+                         int* n_chunks, void** d_w, float** d_ws, int kz_n = 1) {
     std::vector<uint16_t> packed;
     std::vector<float> inv;
-    pack_weights_split(ks, w, cout, cin, *n_cog, *n_chunks, packed, inv);
-    if (!d_w) {                                  // caller concatenates: hand the host vectors back
-        g_pack_tmp.swap(packed);
-        g_inv_tmp.swap(inv);
-        return 0;
-    }
+    pack_weights_split_stacked(ks, w, cout, cin, n_cog, n_chunks, packed, inv, kz_n);
     float* d = nullptr;
     if (upload(ctx, m, reinterpret_cast<const float*>(packed.data()), (packed.size() + 1) / 2, &d)) return 1;
     *d_w = d;
@@ -338,7 +342,7 @@ static int upload_split_weights(tpz_ctx* ctx, tpz_model* m, const SplitKernelInf
 }
 
 // 2xf16 twin of prepare_phases for a 2-D decoder layer conv(cat(upsample2x(a), b)); needs rt.phase (fp32)
-static int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, LayerRT& rt) {
+int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, LayerRT& rt) {
     const tpz_layer& L = rt.L;
     const LayerRT::Phase& ph = rt.phase;
     LayerRT::SplitPhase& sp = rt.sphase;
@@ -368,8 +372,8 @@ static int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, Laye
     }
     const int c1e = sp.low_with_skip ? c1 + 8 : c1;
     std::vector<double> acc;
-    std::vector<float> eff, all_s, sub_w;
-    std::vector<uint16_t> all_w;
+    std::vector<float> eff, all_s, sub_w, inv;
+    std::vector<uint16_t> all_w, packed;
     for (int p = 0; p < (1 << dims); ++p) {
         const int px = p & 1, py = (p >> 1) & 1, pz = dims == 3 ? (p >> 2) & 1 : 0;
         acc.assign((size_t)L.cout * c1 * taps1, 0.0);
@@ -408,12 +412,12 @@ static int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, Laye
         // the K loop mixes the two tensors: conv_split.h MODE 11)
         const bool no_srcmajor = m->dbg.no_srcmajor;
         sp.srcmajor = dims == 3 && sp.low_with_skip && !no_srcmajor && (k1z_n * (c1 / 8)) % sp.ks_low_plain->CC == 0;
-        if (upload_split_weights(ctx, m, sp.low_with_skip ? *sp.ks_low_plain : *sp.ks_low, eff.data(), L.cout, c1e,
-                                 &sp.n_cog_low, &sp.n_chunks_low, nullptr, nullptr, k1z_n, sp.srcmajor ? c1 : 0)) return 1;
-        sp.w_phase_bytes = g_pack_tmp.size() * sizeof(uint16_t);
-        all_w.insert(all_w.end(), g_pack_tmp.begin(), g_pack_tmp.end());
-        g_inv_tmp.resize(chan_pad(L.cout), 0.f);                      // stride chan_pad(cout) per parity
-        all_s.insert(all_s.end(), g_inv_tmp.begin(), g_inv_tmp.end());
+        pack_weights_split_stacked(sp.low_with_skip ? *sp.ks_low_plain : *sp.ks_low, eff.data(), L.cout, c1e, &sp.n_cog_low,
+                                   &sp.n_chunks_low, packed, inv, k1z_n, sp.srcmajor ? c1 : 0);
+        sp.w_phase_bytes = packed.size() * sizeof(uint16_t);
+        all_w.insert(all_w.end(), packed.begin(), packed.end());
+        inv.resize(chan_pad(L.cout), 0.f);                            // stride chan_pad(cout) per parity
+        all_s.insert(all_s.end(), inv.begin(), inv.end());
     }
     // 5x5 (2-D): both parities of an axis read the same 3-tap window, so the four parity kernels share their B
     // operand: one conv with 4*cout virtual output channels on the 128-channel tile (conv_split.h subpix_cout)
@@ -478,7 +482,7 @@ static int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, Laye
 // A conv_split layer whose consumers all read fp32 (the 1-output-channel last conv of the U-Nets runs on the
 // direct kernel) takes the fp32-storing variant when one is compiled; everything else that meets a tensor in the
 // other format has it converted on the device (run_program / slot_as).
-static int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
+int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
     const int nl = (int)m->layers.size();
     // does layer j read slot `slot` as split cells?  (max-pool: whatever its own consumers read)
     std::vector<int> reads(nl, 0);              // per conv layer: 1 = its (non-image) sources are read as split
@@ -687,16 +691,10 @@ static int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
     return 0;
 }
 
-// (the tpz_* entry points below take their C linkage from their declarations in include/topaz_hip.h)
-int tpz_model_load(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
-                   tpz_model** out) {
-    return model_load(ctx, layers, n_layers, h_blob, n_floats, {1}, out);    // slot 0 = the 1-channel input
-}
-
 // Moves every bias-like vector of the model (each chan_pad-ed) into ONE device array and allocates a second one of the same size:
 // a range-scaled pass (tpz_model_forward) writes 2^-s * arena there with one small kernel and reads its biases `bias_shift`
 // floats further on.
-static int build_bias_arena(tpz_ctx* ctx, tpz_model* m) {
+int build_bias_arena(tpz_ctx* ctx, tpz_model* m) {
     std::vector<std::pair<float**, size_t>> vecs;
     for (LayerRT& rt : m->layers) {
         if (rt.L.op != TPZ_OP_CONV) continue;
@@ -733,8 +731,8 @@ static int build_bias_arena(tpz_ctx* ctx, tpz_model* m) {
 // source move up behind the padded first one.  Every real product and every real sum stays what it was (zeros added in
 // fp32): same arithmetic on the same values.  The 1-channel input, 1-output-channel convs, the fused head's single channel
 // and the network's last layer keep their widths.  Returns false when nothing needs padding.
-static bool widen_program(const tpz_layer* layers, int n_layers, const float* blob, size_t n_floats, std::vector<tpz_layer>& out_l,
-                          std::vector<float>& out_b) {
+bool widen_program(const tpz_layer* layers, int n_layers, const float* blob, size_t n_floats, std::vector<tpz_layer>& out_l,
+                   std::vector<float>& out_b) {
     int max_slot = 0;
     for (int i = 0; i < n_layers; ++i)
         max_slot = std::max(max_slot, std::max(std::max(layers[i].src, layers[i].src2), std::max(layers[i].dst, layers[i].res)));
@@ -791,37 +789,8 @@ static bool widen_program(const tpz_layer* layers, int n_layers, const float* bl
     return any;
 }
 
-static int model_load_one(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
-                          const std::vector<int>& preset_chan, tpz_model** out);
-
-// preset_chan: channels of the externally provided slots (slot 0, and tpz_conv's extra sources)
-int model_load(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
-               const std::vector<int>& preset_chan, tpz_model** out) {
-    if (model_load_one(ctx, layers, n_layers, h_blob, n_floats, preset_chan, out)) return 1;
-    tpz_model* m = *out;
-    if (preset_chan.size() != 1 || m->dbg.no_widen || ctx->exact || m->n_conv_split == m->n_conv) return 0;
-    // some layer has no 2xf16 kernel at the widths as given: try the zero-padded program, keep whichever covers more layers
-    std::vector<tpz_layer> wl;
-    std::vector<float> wb;
-    if (!widen_program(layers, n_layers, h_blob, n_floats, wl, wb)) return 0;
-    tpz_model* mw = nullptr;
-    const std::string err_ctx = ctx->err, err_global = last_global_error();
-    if (model_load_one(ctx, wl.data(), n_layers, wb.data(), wb.size(), preset_chan, &mw)) {
-        restore_errors(ctx, err_ctx, err_global);      // the plain model is kept and the load succeeds: no stale error text
-        return 0;
-    }
-    if (mw->n_conv - mw->n_conv_split < m->n_conv - m->n_conv_split) {
-        mw->widened = true;
-        tpz_model_free(m);
-        *out = mw;
-    } else {
-        tpz_model_free(mw);
-    }
-    return 0;
-}
-
-static int model_load_one(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
-                          const std::vector<int>& preset_chan, tpz_model** out) {
+int model_load_one(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
+                   const std::vector<int>& preset_chan, tpz_model** out) {
     if (!ctx || !layers || !out || n_layers < 1) return fail(ctx, "tpz_model_load: bad arguments");
     *out = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -852,6 +821,44 @@ static int model_load_one(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, c
     if (preset_chan.size() == 1 && build_bias_arena(ctx, m)) { tpz_model_free(m); return 1; }
     *out = m;
     return 0;
+}
+
+}  // namespace
+
+// preset_chan: channels of the externally provided slots (slot 0, and tpz_conv's extra sources)
+int model_load(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
+               const std::vector<int>& preset_chan, tpz_model** out) {
+    if (model_load_one(ctx, layers, n_layers, h_blob, n_floats, preset_chan, out)) return 1;
+    tpz_model* m = *out;
+    if (preset_chan.size() != 1 || m->dbg.no_widen || ctx->exact || m->n_conv_split == m->n_conv) return 0;
+    // some layer has no 2xf16 kernel at the widths as given: try the zero-padded program, keep whichever covers more layers
+    std::vector<tpz_layer> wl;
+    std::vector<float> wb;
+    if (!widen_program(layers, n_layers, h_blob, n_floats, wl, wb)) return 0;
+    tpz_model* mw = nullptr;
+    const std::string err_ctx = ctx->err, err_global = last_global_error();
+    if (model_load_one(ctx, wl.data(), n_layers, wb.data(), wb.size(), preset_chan, &mw)) {
+        restore_errors(ctx, err_ctx, err_global);      // the plain model is kept and the load succeeds: no stale error text
+        return 0;
+    }
+    if (mw->n_conv - mw->n_conv_split < m->n_conv - m->n_conv_split) {
+        mw->widened = true;
+        tpz_model_free(m);
+        *out = mw;
+    } else {
+        tpz_model_free(mw);
+    }
+    return 0;
+}
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
+
+int tpz_model_load(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
+                   tpz_model** out) {
+    return model_load(ctx, layers, n_layers, h_blob, n_floats, {1}, out);    // slot 0 = the 1-channel input
 }
 
 void tpz_model_free(tpz_model* m) {
@@ -897,7 +904,3 @@ int tpz_model_out_channels(tpz_model* m, int* C) {
     *C = 1;
     return 0;
 }
-
-// The plane-stacked 3-D kernels address a whole split tensor half with 32-bit byte offsets (conv_split.h fetch): a volume whose
-// widest activation exceeds 4 GiB per half stays on the fp32 kernels.  (No tensor of these networks is larger than the input
-// in voxels: 'same' or valid convolutions, pools.)

@@ -1,15 +1,17 @@
 // NMS driver (kernels: nms.hip).
 #include "rt_internal.h"
 
-extern "C" {
+namespace tpz::rt {
+namespace {
+
 // ---- NMS ------------------------------------------------------------------------------------------
 // Device-side counters of one NMS call: [0 .. NMS_BATCH] lengths of the candidate lists (sweep k of a batch reads [k] and
 // appends its leftovers under [k + 1]); [NMS_VER + k] length of sweep k's verify list; [NMS_SNAP + k] picks before sweep k
 // of the batch (the push after sweep k covers keys[snap[k] .. snap[k + 1])); [NMS_PICKS] picks so far.
 // h_aux: n_aux "near" entries (phase A of a sweep) followed by n_aux2 entries of the whole suppression set (phase B, push):
 // 2-D cells dy * 65536 + (dx + 32768), 3-D flat-index deltas.
-static int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims, int r, const int* h_aux,
-                      int n_aux, int n_aux2, float threshold, int32_t* d_coords, float* d_scores, int cap, int* h_n) {
+int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims, int r, const int* h_aux,
+               int n_aux, int n_aux2, float threshold, int32_t* d_coords, float* d_scores, int cap, int* h_n) {
     const size_t n = (size_t)D * H * W;
     if (n >= ((size_t)1 << 32)) return fail(ctx, "nms: more than 2^32 elements");
     hipStream_t s = ctx->stream;
@@ -97,6 +99,13 @@ static int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, i
     return done(rc);
 }
 
+}  // namespace
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
+
 int tpz_nms_2d(tpz_ctx* ctx, const float* d_score, int H, int W, int r, float threshold, int32_t* d_coords,
                float* d_scores, int cap, int* h_n) {
     if (!ctx || !d_score || H < 1 || W < 1 || r < 0) return fail(ctx, "tpz_nms_2d: bad arguments");
@@ -149,5 +158,3 @@ int tpz_nms_3d(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int r, d
     aux.insert(aux.end(), deltas.begin(), deltas.end());
     return nms_common(ctx, d_score, D, H, W, 3, r, aux.data(), n_near, (int)deltas.size(), threshold, d_coords, d_scores, cap, h_n);
 }
-
-}  // extern "C"

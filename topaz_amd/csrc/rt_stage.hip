@@ -1,7 +1,6 @@
 // Staging ring (pinned host buffer + device buffer + events per slot, one copy stream) and the host-pointer entry points.
 #include "rt_internal.h"
 
-extern "C" {
 // ---- staging ring: pinned host buffer + device buffer + events per slot, one copy stream ----------------------
 struct tpz_stage {
     tpz_ctx* ctx = nullptr;
@@ -16,6 +15,28 @@ struct tpz_stage {
     };
     std::vector<Slot> slots;
 };
+
+namespace tpz::rt {
+namespace {
+
+tpz_stage::Slot* stage_slot(tpz_stage* st, int slot) {
+    return (st && slot >= 0 && slot < (int)st->slots.size()) ? &st->slots[slot] : nullptr;
+}
+
+// host-pointer entry points: two slots of the ctx's own ring (input, output), grown on demand
+int io_stage(tpz_ctx* ctx, size_t bytes, tpz_stage** out) {
+    if (ctx->io_stage && ctx->io_stage->slot_bytes < bytes) { tpz_stage_free(ctx->io_stage); ctx->io_stage = nullptr; }
+    if (!ctx->io_stage && tpz_stage_create(ctx, (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1), 2, &ctx->io_stage)) return 1;
+    *out = ctx->io_stage;
+    return 0;
+}
+
+}  // namespace
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
 
 int tpz_stage_create(tpz_ctx* ctx, size_t slot_bytes, int depth, tpz_stage** out) {
     if (!ctx || !out || slot_bytes == 0 || depth < 1 || depth > 64) return fail(ctx, "tpz_stage_create: bad arguments");
@@ -50,9 +71,6 @@ void tpz_stage_free(tpz_stage* st) {
     }
     if (st->copy) (void)hipStreamDestroy(st->copy);
     delete st;
-}
-static tpz_stage::Slot* stage_slot(tpz_stage* st, int slot) {
-    return (st && slot >= 0 && slot < (int)st->slots.size()) ? &st->slots[slot] : nullptr;
 }
 void* tpz_stage_host_ptr(tpz_stage* st, int slot) { auto* s = stage_slot(st, slot); return s ? s->h : nullptr; }
 void* tpz_stage_device_ptr(tpz_stage* st, int slot) { auto* s = stage_slot(st, slot); return s ? s->d : nullptr; }
@@ -99,13 +117,6 @@ int tpz_stage_wait(tpz_stage* st, int slot) {
     return 0;
 }
 
-// host-pointer entry points: two slots of the ctx's own ring (input, output), grown on demand
-static int io_stage(tpz_ctx* ctx, size_t bytes, tpz_stage** out) {
-    if (ctx->io_stage && ctx->io_stage->slot_bytes < bytes) { tpz_stage_free(ctx->io_stage); ctx->io_stage = nullptr; }
-    if (!ctx->io_stage && tpz_stage_create(ctx, (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1), 2, &ctx->io_stage)) return 1;
-    *out = ctx->io_stage;
-    return 0;
-}
 int tpz_score_2d_host(tpz_model* m, const float* h_in, int H, int W, float* h_out_logits) {
     if (!m || !h_in || !h_out_logits || H < 1 || W < 1) return fail(m ? m->ctx : nullptr, "tpz_score_2d_host: bad arguments");
     tpz_ctx* ctx = m->ctx;
@@ -156,5 +167,3 @@ int tpz_nms_2d_host(tpz_ctx* ctx, const float* h_score, int H, int W, int r, flo
     memcpy(h_scores, (const float*)tpz_stage_host_ptr(st, 1) + (size_t)2 * std::max(cap, 1), k * sizeof(float));
     return tpz_stage_release(st, 1);
 }
-
-}  // extern "C"

@@ -1,7 +1,23 @@
 // Statistics and elementwise entry points: mean / std, GMM fit (topaz normalize), affine, normalise.
 #include "rt_internal.h"
 
-extern "C" {
+namespace tpz::rt {
+namespace {
+
+double beta_logpdf(double x, double a, double b) {
+    // scipy.stats.beta.logpdf: xlog1py(b-1, -x) + xlogy(a-1, x) - betaln(a, b)   (0 * log(0) = 0)
+    const double t1 = (b - 1.0) == 0.0 ? 0.0 : (b - 1.0) * std::log1p(-x);
+    const double t2 = (a - 1.0) == 0.0 ? 0.0 : (a - 1.0) * std::log(x);
+    return t1 + t2 - (std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b));
+}
+
+}  // namespace
+
+}  // namespace tpz::rt
+
+using namespace tpz;
+using namespace tpz::rt;
+
 int tpz_mean_std(tpz_ctx* ctx, const float* d_x, size_t n, int unbiased, float* h_mean_std) {
     if (!ctx || !d_x || !h_mean_std || n == 0) return fail(ctx, "tpz_mean_std: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -24,13 +40,6 @@ int tpz_mean_std(tpz_ctx* ctx, const float* d_x, size_t n, int unbiased, float* 
 // ---- 2-component Gaussian mixture fit (topaz normalize) ---------------------------------------------------
 // topaz/stats.py:87-117 norm_fit + :120-203 gmm_fit (share_var = True), evaluated in fp64 from the sufficient
 // statistics of gmm_pass_kernel: one device pass per EM iteration, the scalar M-step on the host.
-static double beta_logpdf(double x, double a, double b) {
-    // scipy.stats.beta.logpdf: xlog1py(b-1, -x) + xlogy(a-1, x) - betaln(a, b)   (0 * log(0) = 0)
-    const double t1 = (b - 1.0) == 0.0 ? 0.0 : (b - 1.0) * std::log1p(-x);
-    const double t2 = (a - 1.0) == 0.0 ? 0.0 : (a - 1.0) * std::log(x);
-    return t1 + t2 - (std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b));
-}
-
 int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, const double* splits, int n_init,
                 double alpha, double beta, double scale, int num_iters, double tol, double* mus, double* stds,
                 double* pis_out, double* logps) {
@@ -128,5 +137,3 @@ int tpz_normalize(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float st
     HIPCHK(ctx, e);
     return 0;
 }
-
-}  // extern "C"
