@@ -1,7 +1,7 @@
 """Flag tables of the hot-path commands.
 
 The flag names, short options, types, defaults and choices are the drop-in surface of the reference CLI
-(topaz/commands/{extract,denoise,denoise3d,segment,downsample,normalize}.py); they are kept as data here and the
+(topaz/commands/{extract,denoise,denoise3d,segment,downsample,normalize,particle_stack}.py); they are kept as data here and the
 parsers are generated from them.  Help texts are this project's own wording.  Flags that only make sense
 for training are accepted (so existing command lines keep parsing) and rejected at run time.
 """
@@ -146,6 +146,18 @@ NORMALIZE: List[Flag] = [
     (('-o', '--destdir'), dict(help='directory to write into')),
     (('--format',), dict(dest='format_', default='mrc', help='comma separated list of mrc, tiff, png')),
     (('-v', '--verbose'), dict(action='store_true', help='name every processed file')),
+]
+
+
+PARTICLE_STACK: List[Flag] = [
+    (('file',), dict(help='pick table (tab separated: image_name, x_coord, y_coord[, score])')),
+    (('--image-root',), dict(help='directory of the micrographs (default: the working directory)')),
+    (('-o', '--output'), dict(help='particle stack to write (the STAR file goes next to it)')),
+    (('--size',), dict(type=int, help='box size in pixels (required)')),
+    (('--threshold',), dict(type=float, default=-float('inf'), help='keep picks with score >= this (default: -inf)')),
+    (('--resize',), dict(type=int, default=-1, help='downsample every box to this size (default: off)')),
+    (('--image-ext',), dict(default='.mrc', help='extension appended to the image names (default: .mrc)')),
+    (('--metadata',), dict(help='STAR file of per-micrograph metadata merged into the output STAR on MicrographName')),
 ]
 
 

@@ -1,0 +1,20 @@
+"""`topaz particle_stack`: an MRC particle stack and a RELION STAR file from a pick table, the boxes cut, standardised and
+resized on the MI355X (flag surface: _spec.PARTICLE_STACK, mirroring topaz/commands/particle_stack.py:12-28)."""
+
+name = 'particle_stack'
+help = 'extract mrc particle stack given coordinates table'
+
+
+def add_arguments(parser=None):
+    from ._spec import PARTICLE_STACK, build_parser
+    return build_parser(PARTICLE_STACK, help, parser)
+
+
+def main(args):
+    from ..utils.picks import create_particle_stack
+    create_particle_stack(args.file, args.output, args.threshold, args.size, args.resize, args.image_root, args.image_ext,
+                          args.metadata)
+
+
+if __name__ == '__main__':
+    main(add_arguments().parse_args())

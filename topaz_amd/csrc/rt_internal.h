@@ -13,6 +13,7 @@
 //   rt_stats.hip    mean / std, GMM fit, affine, normalise
 //   rt_stage.hip    the staging ring and the host-pointer entry points
 //   rt_nms.hip      the NMS driver
+//   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

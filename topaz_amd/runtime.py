@@ -606,6 +606,29 @@ def filter_2d(x: torch.Tensor, w, bias: float = 0.0, ctx: Optional[Context] = No
     return y
 
 
+def particle_stack(img: torch.Tensor, xy, size: int, resize: int = -1, ops: Optional[np.ndarray] = None,
+                   out: Optional[torch.Tensor] = None, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_particle_stack: the standardised size^2 boxes around the picks xy ([n, 2] int (x, y)) of one micrograph img ([H, W] or
+    [mz, H, W] on the device) -> [n, mz, R, R] fp32 on the device, R = resize (resize <= 0: size).  ops: the host operators of
+    utils.picks.resize_operators(size, resize), needed when R < size.  Asynchronous on the ctx stream."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    img = as_device_f32(img, ctx)
+    mz, H, W = (1,) + tuple(img.shape) if img.dim() == 2 else tuple(img.shape)
+    xy = np.ascontiguousarray(np.asarray(xy, dtype=np.int32).reshape(-1, 2))
+    n = xy.shape[0]
+    R = int(resize) if resize > 0 else int(size)
+    if out is None:
+        out = torch.empty((n, mz, R, R), dtype=torch.float32, device=img.device)
+    assert out.is_contiguous() and out.numel() == n * mz * R * R
+    if ops is not None:
+        ops = np.ascontiguousarray(ops, dtype=np.float32)
+    check(ctx.lib.tpz_particle_stack(ctx.handle, _ptr(img), mz, H, W, xy.ctypes.data_as(C.c_void_p), n, int(size), R,
+                                     ops.ctypes.data_as(C.c_void_p) if ops is not None else C.c_void_p(None), _ptr(out)),
+          ctx.handle)
+    return out
+
+
 def nms(score: torch.Tensor, r: int, threshold: float, scale: float = 1.0, ctx: Optional[Context] = None,
         cap: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """device NMS.  score [H,W] or [D,H,W]; returns (scores[n] fp32, coords[n,dims] int32 (x,y[,z])) on device"""

@@ -30,6 +30,50 @@ def coordinates_to_star(table, image_ext=''):
     return table
 
 
+_STAR_FLOAT_COLUMNS = ('AutopickFigureOfMerit', 'Voltage', 'DetectorPixelSize', 'Magnification', 'AmplitudeContrast')
+
+
+def read_star(f) -> pd.DataFrame:
+    """The first loop of a STAR file as a table of strings (topaz/utils/star.py:15-88): the columns are the `_rln` names
+    without the prefix and trailing `#n`; comment lines are skipped; the coordinates become int, the score and the
+    microscope columns float (ParticleScore is renamed AutopickFigureOfMerit when that column is absent)."""
+    lines = f.readlines()
+    start = next((i + 1 for i, ln in enumerate(lines) if ln.startswith('data_')), None)
+    if start is None:
+        return None
+    lines = lines[start:]
+    for i, ln in enumerate(lines):
+        if ln.startswith('loop_'):
+            lines = lines[i + 1:]
+            break
+    columns, i = [], 0
+    for i, ln in enumerate(lines):
+        ln = ln.strip()
+        if not ln.startswith('_'):
+            break
+        name = ln[1:].split('#', 1)[0]
+        name = (name[3:] if name.startswith('rln') else name).strip()
+        columns.append(name)
+    rows = []
+    for ln in lines[i:]:
+        ln = ln.strip()
+        if ln.startswith('data'):
+            break
+        if ln and not ln.startswith(('#', ';')):
+            rows.append(ln.split())
+    table = pd.DataFrame(rows, columns=columns)
+    if 'ParticleScore' in table.columns and 'AutopickFigureOfMerit' not in table.columns:
+        table['AutopickFigureOfMerit'] = table['ParticleScore']
+        table = table.drop('ParticleScore', axis=1)
+    for name in ('CoordinateX', 'CoordinateY'):
+        if name in table:
+            table[name] = table[name].astype(float).astype(int)
+    for name in _STAR_FLOAT_COLUMNS:
+        if name in table:
+            table[name] = table[name].astype(float)
+    return table
+
+
 def write_star(table, f):
     print('data_images', file=f)
     print('loop_', file=f)
