@@ -147,6 +147,22 @@ int tpz_normalize(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float st
 int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_w, int k, float bias,
                   float* d_out);
 
+/* ---- denoise pre-filters ---------------------------------------------------------------- */
+/* lowpass(x, factor) of topaz/denoise.py:174-197 (2-D) as y = Qh (Qh^T x Qw) Qw^T: h_qh [H][rh] and h_qw [W][rw] (host, float64,
+ * row-major) are orthonormal bases of the kept 1-D frequencies (topaz_amd/denoise.py builds them from the reference's masks).
+ * Four GEMMs with fp64 operands and fp64 accumulation; y is rounded to fp32 once.  Asynchronous; four launches. */
+int tpz_lowpass_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const double* h_qh, int rh, const double* h_qw, int rw,
+                   float* d_out);
+/* spatial_covariance (topaz/denoise.py:22-49) of each of the P x P tiles of correct_spatial_covariance (:129-172; the first H % P
+ * tile rows and W % P tile columns are one pixel longer, each tile is extended by a width/2 halo clipped at the image): h_cov
+ * [P*P][width][width] float64, the lag products summed in fp64 in a fixed order (bit-identical run to run) and divided by the
+ * size of the tile centre.  width must be 11 and every halo'd tile at least width x width.  Two launches; synchronises. */
+int tpz_spatial_cov_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int width, double* h_cov);
+/* the AffineFilter step of correct_spatial_covariance for all tiles at once: a zero-padded width x width cross-correlation of the
+ * whole image where each pixel uses the fp32 weights h_w [P*P][width][width] (host) of its own tile; fp64 accumulation, one
+ * rounding.  Same tile rules as tpz_spatial_cov_2d.  Asynchronous; one launch. */
+int tpz_tile_filter_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int width, const float* h_w, float* d_out);
+
 /* ---- particle stacks ------------------------------------------------------------------- */
 /* replaces the per-particle loop of create_particle_stack (topaz/utils/picks.py:132-163) for the n picks of one micrograph:
  * d_img [mz][H][W], h_xy [n][2] int32 (x, y) on the host, d_out [n][mz][R][R] with R = resize (resize <= 0 or == size: R = size).

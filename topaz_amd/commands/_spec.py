@@ -62,11 +62,11 @@ DENOISE: List[Flag] = [
     (('--hdf',), dict(help=_TRAINING_ONLY)),
     (('--preload',), dict(action='store_true', help=_TRAINING_ONLY)),
     (('--holdout',), dict(type=float, default=0.1, help=_TRAINING_ONLY)),
-    (('--lowpass',), dict(type=float, default=1, help='hard low-pass before denoising (raises: broken upstream)')),
+    (('--lowpass',), dict(type=float, default=1, help='hard low-pass of the raw micrograph before denoising: keep frequencies up to 0.5 / F (F > 1)')),
     (('--gaussian',), dict(type=float, default=0, help='sigma of a Gaussian pre-filter')),
     (('--inv-gaussian',), dict(type=float, default=0, help='sigma of an inverse-Gaussian pre-filter')),
-    (('--deconvolve',), dict(action='store_true', help='covariance deconvolution (raises: broken upstream)')),
-    (('--deconv-patch',), dict(type=int, default=1, help='patches for --deconvolve')),
+    (('--deconvolve',), dict(action='store_true', help='flatten the spatial covariance of the normalised micrograph before denoising')),
+    (('--deconv-patch',), dict(type=int, default=1, help='estimate the --deconvolve filter per tile of an N x N grid (default: 1, the whole micrograph)')),
     (('--pixel-cutoff',), dict(type=float, default=0, help='zero pixels further than this many sigma from the mean')),
     (('-s', '--patch-size'), dict(type=int, default=1024, help='tile size (<1: whole image)')),
     (('-p', '--patch-padding'), dict(type=int, default=500, help='halo around each tile')),

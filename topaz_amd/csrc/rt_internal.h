@@ -14,6 +14,7 @@
 //   rt_stage.hip    the staging ring and the host-pointer entry points
 //   rt_nms.hip      the NMS driver
 //   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
+//   rt_prefilter.hip  denoise pre-filters: fp64 low-pass GEMMs, tile covariances, the per-tile deconvolution filter (kernels there too)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

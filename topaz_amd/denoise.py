@@ -4,11 +4,18 @@ denoise_image (:382-416), denoise_stack (:419-447), denoise_stream (:450-490), d
 
 Patching, per-patch normalisation (torch mean / unbiased std), the network and the stitching all
 run on the device inside tpz_denoise_2d / tpz_denoise_3d; only the image goes in and the denoised
-image comes out.  The reference's lowpass / deconvolve branches crash in v0.3.18
-and raise NotImplementedError here.
+image comes out.
+
+The pre-filters of denoise_image mirror spatial_covariance (:22-49), estimate_unblur_filter (:52-75),
+correct_spatial_covariance (:129-172) and the 2-D lowpass (:174-197).  Both flags crash in v0.3.18 (SURVEY.md P6:
+`lowpass` is shadowed by the parameter, the deconvolution is handed an ndarray); they run here as evidently intended
+(DESIGN.md §9): lowpass as fp64 GEMMs with the projections onto the kept frequencies (tpz_lowpass_2d), the deconvolution
+as per-tile lag covariances (tpz_spatial_cov_2d), the host's float64 filter design and one per-tile filter over the
+whole image (tpz_tile_filter_2d).
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 from typing import List, Optional, Union
@@ -18,7 +25,7 @@ import torch
 
 from . import runtime as rt
 from .denoising.models import DenoiseNet, load_model
-from .filters import GaussianDenoise, InvGaussianFilter
+from .filters import AffineFilter, GaussianDenoise, InvGaussianFilter
 
 
 class Denoise:
@@ -118,13 +125,135 @@ class Denoise3D(Denoise):
         return y.cpu().numpy().astype(np.asarray(tomo).dtype, copy=False)
 
 
+# ---- pre-filters (denoise.py:22-75, 129-197) ------------------------------------------------------------------------------
+DECONV_WIDTH = 11
+
+
+@functools.lru_cache(maxsize=16)
+def lowpass_operator(n: int, factor: float, rfft: bool = False) -> np.ndarray:
+    """Q [n, r] float64 with Q Q^T the projection of lowpass(x, factor) along one axis of length n: orthonormal columns
+    1/sqrt(n), sqrt(2/n) cos(2 pi k j / n), sqrt(2/n) sin(2 pi k j / n) for every kept frequency k >= 1.  The kept set comes from
+    the reference's own expressions (denoise.py:178-189): fftfreq along the rows, rfftfreq along the last axis, a bin is zeroed
+    when |freq| > 0.5 / factor.  For factor > 1 the set is symmetric and misses the Nyquist bin, so the filter is real and
+    separable, y = P_H x P_W.  Cached (read-only): the device upload reads it asynchronously."""
+    if not factor > 1:
+        raise ValueError(f'lowpass factor {factor}: only factors > 1 filter (denoise.py:386)')
+    freq = np.fft.rfftfreq(n) if rfft else np.fft.fftfreq(n)
+    keep = ~(np.abs(freq) > 0.5 / factor)
+    half = (n - 1) // 2                                    # positive frequencies below Nyquist
+    ks = [k for k in range(1, half + 1) if keep[k]]
+    assert keep[0] and (n % 2 or not keep[n // 2])
+    assert rfft or all(keep[n - k] == keep[k] for k in range(1, half + 1))
+    j = np.arange(n, dtype=np.int64)
+    q = np.empty((n, 1 + 2 * len(ks)), dtype=np.float64)
+    q[:, 0] = 1.0 / np.sqrt(n)
+    if ks:
+        t = (2 * np.pi / n) * (np.outer(j, np.asarray(ks, dtype=np.int64)) % n)   # exact phase reduction
+        q[:, 1::2] = np.sqrt(2.0 / n) * np.cos(t)
+        q[:, 2::2] = np.sqrt(2.0 / n) * np.sin(t)
+    q.flags.writeable = False
+    return q
+
+
+def _device_ctx():
+    return rt.get_context()
+
+
+def _like(y: torch.Tensor, x):
+    """the device result in the form the input came in: numpy (x's dtype), a host tensor, or the device tensor itself"""
+    if isinstance(x, np.ndarray):
+        return y.cpu().numpy().astype(x.dtype, copy=False)
+    if isinstance(x, torch.Tensor) and x.device.type == 'cpu':
+        return y.cpu()
+    return y
+
+
+def lowpass(x, factor=1, dims=2):
+    """hard low-pass of a 2-D image (denoise.py:174-197): every rfftn bin with |fftfreq| > 0.5 / factor along the rows or
+    |rfftfreq| > 0.5 / factor along the columns is zeroed, evaluated as the exact fp64 projection P_H x P_W on the device and
+    rounded to float32 once.  numpy or tensor in, the same form out.  factor <= 1 returns x unchanged (the caller's
+    `lowpass > 1` test, denoise.py:386)."""
+    if dims != 2 or np.ndim(x) != 2:
+        raise NotImplementedError('lowpass: only the 2-D filter is implemented (nothing calls the 3-D form)')
+    if not factor > 1:
+        return x
+    H, W = x.shape
+    y = rt.lowpass_2d(rt.as_device_f32(x, _device_ctx()), lowpass_operator(H, float(factor)),
+                      lowpass_operator(W, float(factor), rfft=True))
+    return _like(y, x)
+
+
+_lowpass = lowpass          # denoise_image's parameter of the same name shadows the function (the reference's crash)
+
+
+def deconv_tiles(H: int, W: int, patch: int = 1, width: int = DECONV_WIDTH):
+    """(N, M, halo'd tile rows, halo'd tile columns) of correct_spatial_covariance (denoise.py:135-158): N / M the tile
+    heights / widths (the first H % patch / W % patch one longer), each halo'd span (start, length) clipped at the image.
+    patch <= 1 is the whole image.  Raises ValueError when a halo'd tile is smaller than the filter (the reference fails inside
+    conv2d)."""
+    P = max(1, int(patch))
+    p = width // 2
+    spans = []
+    for n in (H, W):
+        q, r = divmod(n, P)
+        sizes = [q + (1 if t < r else 0) for t in range(P)]
+        starts = [sum(sizes[:t]) for t in range(P)]
+        spans.append((sizes, [(max(0, a - p), min(n, a + m + p) - max(0, a - p)) for a, m in zip(starts, sizes)]))
+    (N, ry), (M, rx) = spans
+    h, w = min(s[1] for s in ry), min(s[1] for s in rx)
+    if h < width or w < width:
+        raise ValueError(f'--deconvolve: a {H} x {W} image in {P} x {P} patches (--deconv-patch {P}) has a {h} x {w} tile '
+                         f'(halo included), smaller than the {width} x {width} filter')
+    return N, M, ry, rx
+
+
+def unblur_filter(cov: np.ndarray) -> np.ndarray:
+    """w_inv of estimate_unblur_filter (denoise.py:61-73) in float64 from the lag covariances cov [width, width]: the power
+    spectrum Re fft2(ifftshift(cov)), non-positive bins and the DC bin set to 1, then fftshift(ifft2(ps^-1/2)).real"""
+    ps = np.fft.fft2(np.fft.ifftshift(np.asarray(cov, dtype=np.float64))).real
+    ps = np.where(ps <= 0, 1.0, ps)
+    ps[0, 0] = 1.0
+    return np.fft.fftshift(np.fft.ifft2(1.0 / np.sqrt(ps))).real
+
+
+def spatial_covariance(x, n=DECONV_WIDTH, s=11) -> np.ndarray:
+    """the n x n lag covariances of a 2-D image (denoise.py:22-49), float64 from fp64 sums on the device"""
+    return rt.spatial_cov_2d(rt.as_device_f32(x, _device_ctx()), 1, n)[0]
+
+
+def estimate_unblur_filter(x, width=DECONV_WIDTH, s=11):
+    """(AffineFilter(w_inv), cov) of denoise.py:52-75; cov float64"""
+    cov = spatial_covariance(x, n=width, s=s)
+    return AffineFilter(unblur_filter(cov)), cov
+
+
+def correct_spatial_covariance(x, width=DECONV_WIDTH, s=11, patch=1):
+    """denoise.py:129-172 called as intended (on a tensor): each of the patch x patch tiles (halo width // 2) is filtered with
+    the fp32-rounded unblurring filter of its own covariances.  Three launches whatever the patch count: the covariances of
+    all tiles, then one zero-padded filter over the whole image with each pixel's tile weights (equal to filtering each halo'd
+    tile and keeping its centre).  numpy or tensor in, the same form out (float32)."""
+    if np.ndim(x) != 2:
+        raise NotImplementedError('correct_spatial_covariance: only 2-D images')
+    H, W = x.shape
+    P = max(1, int(patch))
+    deconv_tiles(H, W, P, width)
+    xd = rt.as_device_f32(x, _device_ctx())
+    cov = rt.spatial_cov_2d(xd, P, width)
+    w = np.stack([unblur_filter(c) for c in cov]).astype(np.float32)
+    y = rt.tile_filter_2d(xd, w, P)
+    return y.cpu().numpy() if isinstance(x, np.ndarray) else _like(y, x)
+
+
 def denoise_image(mic: np.ndarray, models: List[Denoise], lowpass=1, cutoff=0, gaus: GaussianDenoise = None,
                   inv_gaus: InvGaussianFilter = None, deconvolve=False, deconv_patch=1, patch_size=-1, padding=0,
                   normalize=False, use_cuda=True) -> np.ndarray:
-    """denoise_image (denoise.py:382-416).  numpy mean / POPULATION std here (unlike _denoise)."""
-    if lowpass > 1:
-        raise NotImplementedError('lowpass: crashes in the reference (denoise.py:386 shadows the function)')
+    """denoise_image (denoise.py:382-416).  numpy mean / POPULATION std here (unlike _denoise).  The pre-filters run as
+    evidently intended: lowpass on the raw micrograph, deconvolution on the normalised one."""
     mic = np.asarray(mic)
+    if deconvolve and gaus is None and inv_gaus is None:
+        deconv_tiles(*mic.shape, deconv_patch)              # refused before anything runs
+    if lowpass > 1:
+        mic = _lowpass(mic, lowpass)
     mu, std = mic.mean(), mic.std()
     x = (mic - mu) / std
     if cutoff > 0:
@@ -134,7 +263,7 @@ def denoise_image(mic: np.ndarray, models: List[Denoise], lowpass=1, cutoff=0, g
     elif inv_gaus is not None:
         x = inv_gaus.apply(x)
     elif deconvolve:
-        raise NotImplementedError('deconvolve: crashes in the reference (denoise.py:404 on ndarray input)')
+        x = correct_spatial_covariance(x, patch=deconv_patch)
     if len(models) == 0:
         # `-m none` (commands/denoise.py:100-106 still builds a Denoise around no model): the pre-filtered image passes through
         out = np.asarray(x, dtype=np.float32)
@@ -148,16 +277,24 @@ def denoise_image(mic: np.ndarray, models: List[Denoise], lowpass=1, cutoff=0, g
 
 
 def denoise_image_device(x: torch.Tensor, models: List[Denoise], patch_size: int = -1, padding: int = 0,
-                         normalize: bool = False) -> torch.Tensor:
+                         normalize: bool = False, lowpass: float = 1, deconvolve: bool = False,
+                         deconv_patch: int = 1) -> torch.Tensor:
     """denoise_image (denoise.py:382-416) for the plain case -- no pixel cutoff, no Gaussian / inverse filter -- with the
     micrograph staying on the device: population mean / std (the reference's numpy statistics, here a deterministic fp64
     reduction on the GPU), (x - mu) / std, the networks' average, then either re-normalisation or std * y + mu.  The CLI path
     spends no host pass over the 16.7 M pixels this way (the numpy version costs ~130 ms per 4096^2 micrograph, 7x the GPU
-    work of the network)."""
+    work of the network).  lowpass > 1 filters the raw micrograph first, deconvolve the normalised one before the networks
+    (the reference's order); with no model the pre-filtered image passes through (`-m none`)."""
     from . import runtime as rt
+    if deconvolve:
+        deconv_tiles(*x.shape, deconv_patch)                # refused before anything runs
+    if lowpass > 1:
+        x = _lowpass(x, lowpass)
     mu, std = rt.mean_std(x, unbiased=False)
     xn = rt.normalize(x, mu, std)              # (x - mu) / std as numpy rounds it; std == 0 -> inf / nan like upstream
-    out = None
+    if deconvolve:
+        xn = correct_spatial_covariance(xn, patch=deconv_patch)
+    out = None if models else xn
     for model in models:
         y = model.denoise_device(xn, patch_size, padding)
         out = y if out is None else out + y
@@ -251,10 +388,14 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
     jobs = [_Job(i, micrographs[i], _output_path(micrographs[i], output_path, suffix, '.' + format))
             for i in parallel.shard_indices(len(micrographs), rank, world)]
 
-    plain = (models and lowpass <= 1 and pixel_cutoff <= 0 and gaus is None and inv_gaus is None and not deconvolve and
-             all(m.dims == 2 for m in models))
-    if plain:
-        return _denoise_stream_device(jobs, models, patch_size, padding, normalize, len(micrographs), return_images)
+    models = models or []
+    # every pass over the pixels on the device unless a pixel cutoff or a Gaussian asks for the host path; `-m none` without
+    # a pre-filter keeps the host pass-through
+    on_device = (pixel_cutoff <= 0 and gaus is None and inv_gaus is None and all(m.dims == 2 for m in models) and
+                 (len(models) > 0 or lowpass > 1 or deconvolve))
+    if on_device:
+        return _denoise_stream_device(jobs, models, patch_size, padding, normalize, len(micrographs), return_images,
+                                      lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch)
 
     def read(job):
         loaded = load_image(job.src, make_image=False)
@@ -275,7 +416,8 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
 
 
 def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: int, padding: int, normalize: bool, total: int,
-                           return_images: bool = False) -> list:
+                           return_images: bool = False, lowpass: float = 1, deconvolve: bool = False,
+                           deconv_patch: int = 1) -> list:
     """the plain `topaz denoise` loop with every pass over the pixels on the device: a reader thread decodes micrograph i+1
     into pinned memory and queues its upload (extract.ImageFeed), the GPU denoises micrograph i (denoise_image_device), its
     result is copied into a pinned slot by the copy stream and a writer thread writes micrograph i-1 from there."""
@@ -287,7 +429,7 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
     results = []
     if not jobs:
         return results
-    ctx = models[0].model.device_model.ctx
+    ctx = models[0].model.device_model.ctx if models else rt.get_context()
     by_src = {}
     for job in jobs:
         by_src.setdefault(job.src, []).append(job)
@@ -318,7 +460,8 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
     try:
         for n, (path, x, header, extended) in enumerate(ImageFeed([j.src for j in jobs], ctx, headers=True)):
             job = by_src[path].pop(0)
-            y = denoise_image_device(x, models, patch_size, padding, normalize)
+            y = denoise_image_device(x, models, patch_size, padding, normalize, lowpass=lowpass, deconvolve=deconvolve,
+                                     deconv_patch=deconv_patch)
             nbytes = y.numel() * 4
             if out_stage is None or nbytes > out_bytes:
                 # (a larger image: a new ring; the old one is closed once the writer has drained it)

@@ -606,6 +606,47 @@ def filter_2d(x: torch.Tensor, w, bias: float = 0.0, ctx: Optional[Context] = No
     return y
 
 
+def lowpass_2d(x: torch.Tensor, qh: np.ndarray, qw: np.ndarray, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_lowpass_2d: y = qh (qh^T x qw) qw^T in fp64, rounded to fp32 once.  x [H, W]; qh [H, rh] and qw [W, rw] float64 host
+    operators (denoise.lowpass_operator).  The caller keeps qh / qw alive (the operator cache does).  Asynchronous."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    H, W = x.shape
+    assert qh.dtype == np.float64 and qw.dtype == np.float64 and qh.flags.c_contiguous and qw.flags.c_contiguous
+    assert qh.shape[0] == H and qw.shape[0] == W
+    y = torch.empty_like(x)
+    check(ctx.lib.tpz_lowpass_2d(ctx.handle, _ptr(x), H, W, qh.ctypes.data_as(C.c_void_p), qh.shape[1],
+                                 qw.ctypes.data_as(C.c_void_p), qw.shape[1], _ptr(y)), ctx.handle)
+    return y
+
+
+def spatial_cov_2d(x: torch.Tensor, patch: int = 1, width: int = 11, ctx: Optional[Context] = None) -> np.ndarray:
+    """tpz_spatial_cov_2d: the lag covariances of the patch x patch tiles of x -> [patch * patch, width, width] float64 (host)"""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    H, W = x.shape
+    cov = np.empty((patch * patch, width, width), dtype=np.float64)
+    check(ctx.lib.tpz_spatial_cov_2d(ctx.handle, _ptr(x), H, W, int(patch), int(width), cov.ctypes.data_as(C.c_void_p)),
+          ctx.handle)
+    return cov
+
+
+def tile_filter_2d(x: torch.Tensor, w: np.ndarray, patch: int = 1, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_tile_filter_2d: zero-padded cross-correlation of x with the fp32 weights w [patch * patch, k, k] of each pixel's tile"""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    H, W = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    assert w.shape == (patch * patch, w.shape[-1], w.shape[-1])
+    y = torch.empty_like(x)
+    check(ctx.lib.tpz_tile_filter_2d(ctx.handle, _ptr(x), H, W, int(patch), w.shape[-1], w.ctypes.data_as(C.c_void_p), _ptr(y)),
+          ctx.handle)
+    return y
+
+
 def particle_stack(img: torch.Tensor, xy, size: int, resize: int = -1, ops: Optional[np.ndarray] = None,
                    out: Optional[torch.Tensor] = None, ctx: Optional[Context] = None) -> torch.Tensor:
     """tpz_particle_stack: the standardised size^2 boxes around the picks xy ([n, 2] int (x, y)) of one micrograph img ([H, W] or
