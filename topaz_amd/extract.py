@@ -13,7 +13,8 @@ stream_inputs :259-263, extract_particles :266-367) -- over a different engine:
 
 Differences from the reference, all deliberate: there is no CPU path (`device` < 0 raises); worker pools are accepted and
 ignored (the suppression is on the GPU); with WORLD_SIZE > 1 the micrographs are dealt round-robin to the ranks and the
-pick tables gathered to rank 0 over RCCL (topaz_amd/parallel.py); an existing directory given as `-o` receives
+pick tables gathered to rank 0 over RCCL (topaz_amd/parallel.py), as are the per-image records of the `--targets` radius
+search, which rank 0 pools in single-process order; an existing directory given as `-o` receives
 `extracted_particles.txt` (upstream: `sys.path.join` typo, extract.py:318) and `COORDS/` is created (upstream forgets).
 The patched suppression branch of NonMaximumSuppression cannot run upstream (extract.py:55 unpacks three values from a
 two-tuple; the default 64/32 tiling has step 0): it is implemented here as written-to-be, tile by tile on the device.
@@ -121,18 +122,33 @@ class RadiusSearch:
         self.pairs = [(score, targets.loc[targets.image_name == name, ['x_coord', 'y_coord']].values)
                       for name, score in scores.items()]
 
-    def evaluate(self, radius) -> Tuple[float, float, int, int]:
-        sq_err, n_targets, hit_flags, hit_scores = 0.0, 0, [], []
+    def evaluate_local(self, radius) -> List[Tuple[np.ndarray, np.ndarray, float, int]]:
+        """one record per map of this object, in the order of `self.pairs`: (hit flag of every pick fp32[n], its score
+        fp32[n], summed squared distance of the hits to their targets, number of targets).  What a rank of a sharded job
+        computes; `reduce` pools the records of every rank."""
+        records = []
         for score, target in self.pairs:
             s, coords = _suppress(score, radius * 2 if self.dims == 3 else radius, self.threshold, self.dims)
             matched, dist = match_coordinates(target, coords, radius if self.match_radius is None else self.match_radius)
-            sq_err += float(np.sum(dist[matched == 1] ** 2))
+            records.append((matched, s, float(np.sum(dist[matched == 1] ** 2)), len(target)))
+        return records
+
+    @staticmethod
+    def reduce(records) -> Tuple[float, float, int, int]:
+        """(auprc, rmse, hits, targets) of records given IN SINGLE-PROCESS IMAGE ORDER: the average precision sorts by score
+        with ties kept in input order and the squared error is a float sum, so both depend on it"""
+        sq_err, n_targets, hit_flags, hit_scores = 0.0, 0, [], []
+        for matched, s, err, n in records:
+            sq_err += err
             hit_flags.append(matched)
             hit_scores.append(s)
-            n_targets += len(target)
+            n_targets += n
         hits, preds = np.concatenate(hit_flags), np.concatenate(hit_scores)
         n_hit = hits.sum()
         return average_precision(hits, preds, N=n_targets), np.sqrt(sq_err / n_hit), int(n_hit), n_targets
+
+    def evaluate(self, radius) -> Tuple[float, float, int, int]:
+        return self.reduce(self.evaluate_local(radius))
 
     @staticmethod
     def line(radius, result) -> str:
@@ -147,6 +163,31 @@ class RadiusSearch:
             print(self.line(r, res))
         r = int(np.argmax(curve))
         return r, curve[r]
+
+
+def _radius_over_ranks(search: RadiusSearch, image_ids: Sequence[int], radius: int, lo: int, hi: int, step: int, rank: int,
+                       local_rank: int) -> int:
+    """`--targets` with WORLD_SIZE > 1.  Every rank evaluates the maps it holds (`image_ids`: their positions in the
+    single-process image order; none is fine) at every radius of the sweep, or at the one given radius; ONE exchange moves all
+    records to rank 0 (parallel.gather_radius_records), which pools them per radius in that order -- the arithmetic of one
+    process, bit for bit --, prints what one process prints and broadcasts the radius every rank then extracts at."""
+    dev = parallel.collective_device(local_rank)
+    searching = radius < 0
+    radii = list(range(lo, hi + 1, step)) if searching else [radius]
+    if searching and rank == 0:
+        report('Finding optimal radius for extraction')
+    gathered = parallel.gather_radius_records([search.evaluate_local(r) for r in radii], image_ids, dev)
+    if rank == 0:
+        curve = np.full(hi + 1, -1.0)
+        for r, records in zip(radii, gathered):
+            res = RadiusSearch.reduce(records)
+            print(RadiusSearch.line(r, res))
+            if searching:
+                curve[r] = res[0]
+        if searching:
+            radius = int(np.argmax(curve))
+            report(f'Optimal radius found: {radius} with AUPRC: {curve[radius]}')
+    return parallel.broadcast_int(radius, 0, dev)
 
 
 def extract_auprc(targets, scores, radius, threshold, match_radius=None, pool=None, dims=2):
@@ -434,12 +475,17 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
 
     if targets is not None:
         # every score map is needed at once (they stay in HBM); the table is keyed by the paths as given (extract.py:284-290)
-        if world > 1:
-            raise NotImplementedError('--targets (radius search / validation) runs in a single process')
         maps = dict(maps)
         table = pd.read_csv(targets, sep='\t')
-        search = RadiusSearch(table, {n: maps[n] for n in table.image_name.unique() if n in maps}, threshold, match_radius, dims)
-        if radius < 0:
+        # the images of the table in single-process order; each is evaluated by the rank that scored it (the last one, had the
+        # list named it twice) and carries its position in that order through the exchange
+        owner = {p: i for i, p in enumerate(paths)}
+        named = [n for n in table.image_name.unique() if n in owner]
+        held = [g for g, n in enumerate(named) if owner[n] % world == rank]
+        search = RadiusSearch(table, {named[g]: maps[named[g]] for g in held}, threshold, match_radius, dims)
+        if world > 1:
+            radius = _radius_over_ranks(search, held, radius, min_radius, max_radius, step, rank, local_rank)
+        elif radius < 0:
             report('Finding optimal radius for extraction')
             radius, auprc = search.best(min_radius, max_radius, step)
             report(f'Optimal radius found: {radius} with AUPRC: {auprc}')

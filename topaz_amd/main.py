@@ -21,7 +21,8 @@ def main(argv=None):
     n = _ranks_to_launch(args)
     if n > 1:
         # `--gpus N` / `-d -2`: become the launcher -- N rank processes of this same command line, one per GPU; every
-        # command shards its input list over the ranks (parallel.shard_indices), extract gathers the pick tables
+        # command shards its input list over the ranks (parallel.shard_indices), extract gathers the pick tables and, with
+        # --targets, the per-image records of the radius sweep
         from . import parallel
         cmd = [sys.executable, '-m', 'topaz_amd'] + list(sys.argv[1:] if argv is None else argv)
         listfile, env = None, None

@@ -1,6 +1,7 @@
 """Multi-GPU layer: micrographs shard embarrassingly (one image per rank at a time, rank r takes
-images i = r (mod world)); the only exchange step is the gather of the per-image pick tables to
-rank 0 for the single-TSV output mode of `topaz extract` (topaz/extract.py:321-354).
+images i = r (mod world)); the exchange steps are the gather of the per-image pick tables to
+rank 0 for the single-TSV output mode of `topaz extract` (topaz/extract.py:321-354) and, with
+`--targets`, one gather of every rank's per-image hit / score records of the whole radius sweep.
 
 One process per GPU; torch.distributed backend 'nccl' (= RCCL over xGMI on ROCm) on the GPU box,
 'gloo' in the CPU tests.  The reference has no distributed code; this is new.
@@ -11,6 +12,7 @@ import os
 import sys
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -402,3 +404,70 @@ def gather_pick_tables(image_ids: Sequence[int], scores: Sequence[torch.Tensor],
             out[iid] = (blk[:, d].contiguous().view(torch.float32).clone(), blk[:, :d].clone())
             off += n
     return out
+
+
+def gather_radius_records(per_radius_records: Sequence[Sequence[tuple]], image_ids: Sequence[int], device: torch.device,
+                          dst: int = 0) -> Optional[list]:
+    """Gather the `--targets` records of a whole radius sweep to rank `dst`.
+
+    per_radius_records[k][j] is RadiusSearch.evaluate_local's record of this rank's j-th map at the k-th radius -- (hit flags
+    fp32 [n], scores fp32 [n], squared error, number of targets) -- and image_ids[j] that map's position in the single-process
+    image order.  A rank without maps passes empty lists and takes part all the same.
+    Exchange, as in gather_pick_tables: one all_gather of (radii, records, picks) per rank fixes the stride, then ONE gather
+    moves every rank's sweep as a single int64 buffer, padded to the largest rank: `max_rec` index rows of (radius slot, image
+    id, n_picks, n_targets), `max_rec` squared errors (float64 bits), and per record its n flags followed by its n scores
+    (float32 bits, two to a word) -- 8 n + 40 bytes per image and radius.  Every bit pattern travels unchanged.
+    Returns on dst, per radius, the records sorted by image id; None on the other ranks."""
+    n_slots = len(per_radius_records)
+    flat = [(k, int(i), rec) for k, records in enumerate(per_radius_records) for i, rec in zip(image_ids, records)]
+    if not (dist.is_available() and dist.is_initialized()):
+        return [[rec for _, _, rec in sorted((f for f in flat if f[0] == k), key=lambda f: f[1])] for k in range(n_slots)]
+    world, rank = dist.get_world_size(), dist.get_rank()
+    n_rec = len(flat)
+    n_picks = int(sum(len(rec[0]) for _, _, rec in flat))
+    metas_t = torch.zeros(world * 3, dtype=torch.int64, device=device)
+    dist.all_gather_into_tensor(metas_t, torch.tensor([n_slots, n_rec, n_picks], dtype=torch.int64, device=device))
+    metas = metas_t.view(world, 3).cpu().tolist()
+    if any(m[0] != n_slots for m in metas):
+        raise RuntimeError(f'the ranks disagree on the number of radii: {[m[0] for m in metas]}')
+    max_rec = max(1, max(m[1] for m in metas))
+    max_picks = max(1, max(m[2] for m in metas))
+    # packed on the host, where the records are (the Hungarian matching produced them there): one copy to the collective's device
+    buf = np.zeros(5 * max_rec + max_picks, dtype=np.int64)
+    index = buf[:4 * max_rec].reshape(max_rec, 4)
+    sq_err = buf[4 * max_rec:5 * max_rec].view(np.float64)
+    values = buf[5 * max_rec:].view(np.float32)
+    off = 0
+    for j, (k, i, (flags, scores, err, n_targets)) in enumerate(flat):
+        n = len(flags)
+        index[j] = (k, i, n, n_targets)
+        sq_err[j] = err
+        values[off:off + n] = flags
+        values[off + n:off + 2 * n] = scores
+        off += 2 * n
+    t = torch.from_numpy(buf).to(device)
+    bufs = [torch.zeros_like(t) for _ in range(world)] if rank == dst else None
+    dist.gather(t, bufs, dst=dst)
+    if rank != dst:
+        return None
+    allb = torch.stack(bufs, 0).cpu().numpy()                  # one copy of everything gathered
+    slots: List[list] = [[] for _ in range(n_slots)]
+    for r in range(world):
+        index = allb[r, :4 * max_rec].reshape(max_rec, 4)
+        sq_err = allb[r, 4 * max_rec:5 * max_rec].view(np.float64)
+        values = allb[r, 5 * max_rec:].view(np.float32)
+        off = 0
+        for j in range(metas[r][1]):
+            k, i, n, n_targets = (int(v) for v in index[j])
+            slots[k].append((i, (values[off:off + n].copy(), values[off + n:off + 2 * n].copy(), float(sq_err[j]), n_targets)))
+            off += 2 * n
+    return [[rec for _, rec in sorted(s, key=lambda e: e[0])] for s in slots]
+
+
+def broadcast_int(value: int, src: int = 0, device: Optional[torch.device] = None) -> int:
+    """rank `src`'s integer on every rank (one broadcast); `value` itself without a process group"""
+    if not (dist.is_available() and dist.is_initialized()):      # (a 1-rank group takes the collective path too)
+        return int(value)
+    t = torch.tensor([int(value)], dtype=torch.int64, device=device)
+    dist.broadcast(t, src=src)
+    return int(t.item())
