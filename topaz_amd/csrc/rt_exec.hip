@@ -98,21 +98,49 @@ int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const
 
 int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops);
 
-// window of a launch from the part of the layer's tensor that is needed (`need` in the tensor's coordinates, `scale` = 2 for the
-// low-resolution lattice of a per-parity / sub-pixel launch, `grow_x` extra columns at the right: the column kernel of a last
-// conv); flops are scaled by the fraction of the lattice that is computed
+// What every 2xf16 launch shares.  `in`: cells1 cells of g_in; the launch computes the lattice `lat` (kz taps along z, kz = 0: a 2-D
+// launch; `pad` on every axis), element o of which is element o * os (+ the parity) of the full output tensor `full`.  The window is
+// the whole lattice, Dlat its depth.  The caller adds its operands, a second source and whatever else is particular to it.
+SplitArgs split_args(tpz_ctx* ctx, const void* in, int cells1, const Dhw& g_in, int cout, const Dhw& lat, int os, const Dhw& full,
+                     int kz, int pad, float slope) {
+    SplitArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = reinterpret_cast<const uint4*>(in);
+    a.zeros = ctx->d_zeros;
+    a.flag = ctx->d_flag;
+    a.slope = slope;
+    a.cells_in = a.cells_in1 = cells1;
+    a.Hin = a.H1 = g_in.H; a.Win = a.W1 = g_in.W;
+    a.Cout = cout; a.cells_out = (int)split_cells(cout);
+    a.Hout = a.wy1 = lat.H; a.Wout = a.wx1 = lat.W;
+    a.pad_x = a.pad_y = pad;
+    a.os = os; a.Hfull = full.H; a.Wfull = full.W;
+    a.cog_inner = 1;
+    if (kz > 0) { a.KZ = kz; a.pad_z = pad; a.Din = g_in.D; a.Dout = a.Dlat = lat.D; a.Dfull = full.D; a.Dres = 1; }
+    return a;
+}
+Dhw dhw(const Slot& s) { return {s.D, s.H, s.W}; }
+
+// narrows the window of a launch to the part of the layer's tensor that is needed (`need` in the tensor's coordinates, `scale` = 2
+// for the low-resolution lattice of a per-parity / sub-pixel launch, `grow_x` extra columns at the right: the column kernel of a
+// last conv)
 void set_window(SplitArgs& a, const Rect& need, int scale = 1, int grow_x = 0) {
     if (!need.on) return;
     a.wy0 = need.y0 / scale; a.wx0 = need.x0 / scale;
     a.wy1 = std::min(a.Hout, (need.y1 + scale - 1) / scale);
     a.wx1 = std::min(a.Wout, (need.x1 + scale - 1) / scale + grow_x);
     a.wy1 = std::max(a.wy1, a.wy0 + 1); a.wx1 = std::max(a.wx1, a.wx0 + 1);
-    a.wy1 = -a.wy1;            // (marks the window as set: launch_split flips it back)
     if (a.Dout > 1) {          // plane-stacked 3-D: the planes of the box
-        a.Dlat = a.Dout;
         a.wz0 = std::min(a.Dout - 1, need.z0 / scale);
         a.Dout = std::max(a.wz0 + 1, std::min(a.Dout, (need.z1 + scale - 1) / scale)) - a.wz0;
     }
+}
+
+// the FLOP a launch executes of its layer's: the share of the lattice that lies in its window
+double window_flops(const SplitArgs& a, double flops) {
+    flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
+    if (a.Dlat > 0) flops *= (double)a.Dout / a.Dlat;
+    return flops;
 }
 
 
@@ -123,12 +151,7 @@ int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops) {
     const int di = dil == 1 ? 0 : dil == 2 ? 1 : 2;
     if (!names[di][epi][0])
         snprintf(names[di][epi], sizeof names[di][epi], "conv_split_rw_kernel<K=3x3,D=%d,MT=32,EPI=%d> (weights resident)", dil, epi);
-    if (a.wy1 < 0) {
-        a.wy1 = -a.wy1;
-        flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
-    } else {
-        a.wy0 = a.wx0 = 0; a.wy1 = a.Hout; a.wx1 = a.Wout;
-    }
+    flops = window_flops(a, flops);
     a.tiles_x = (a.wx1 - a.wx0 + 31) / 32;
     a.tiles_y = (a.wy1 - a.wy0 + 8 * dil - 1) / (8 * dil) * dil;
     const long long nt = (long long)a.tiles_x * a.tiles_y;
@@ -151,6 +174,43 @@ int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops) {
 
 }  // namespace
 
+unsigned split_forms(const tpz_model* m, int i) {
+    const LayerRT& rt = m->layers[i];
+    if (rt.folded_into >= 0 && m->layers[rt.folded_into].ks_fold) return 1u << FORM_FOLDED_AWAY;
+    return (rt.ks_stem ? 1u << FORM_STEM : 0) | (rt.ks_last ? 1u << FORM_LAST : 0) | (rt.sphase.valid ? 1u << FORM_PARITY : 0) |
+           (rt.ks && rt.ks_fold ? 1u << FORM_SPLIT_FOLD : 0) | (rt.ks ? 1u << FORM_SPLIT : 0) |
+           (rt.ki_stem_split ? 1u << FORM_FP32_STEM_SPLIT : 0);
+}
+
+// Which kernels run conv layer i of a pass (split: a 2xf16 pass), and in which format it reads and writes its tensors.  Of the forms
+// the layer was loaded with, the first that this run's shapes and formats allow, in the order below.  (prepare_split gives a layer
+// at most one of STEM / LAST / SPLIT-or-PARITY / FP32_STEM_SPLIT: they need a 1-channel source, no MFMA kernel, a multi-channel MFMA
+// kernel and a 1-channel source without ks_stem; ks_fold needs a residual and ks_pool none, so a folded layer never fuses a pool.)
+ConvPlan conv_plan(const tpz_model* m, int i, bool split, const Dhw& g1, const Dhw* g2, bool split1, bool fold_set) {
+    const LayerRT& rt = m->layers[i];
+    const tpz_layer& L = rt.L;
+    const unsigned f = split ? split_forms(m, i) : 0;
+    auto has = [&](ConvForm c) { return (f >> c & 1u) != 0; };
+    // the per-parity form needs the skip source to be exactly twice the upsampled one
+    const bool exact2x = g2 && g2->H == 2 * g1.H && g2->W == 2 * g1.W && (L.dims == 2 || g2->D == 2 * g1.D);
+    ConvPlan p;
+    if (has(FORM_FOLDED_AWAY)) p.form = FORM_FOLDED_AWAY;
+    else if (has(FORM_STEM) && !split1) p.form = FORM_STEM;
+    else if (has(FORM_LAST)) p.form = FORM_LAST;
+    else if (has(FORM_PARITY) && exact2x) p.form = FORM_PARITY;
+    else if (has(FORM_SPLIT_FOLD) && rt.fold_src >= 0 && fold_set) p.form = FORM_SPLIT_FOLD;
+    else if (has(FORM_SPLIT)) p.form = FORM_SPLIT;
+    else if (has(FORM_FP32_STEM_SPLIT)) p.form = FORM_FP32_STEM_SPLIT;
+    const bool on_ks = p.form == FORM_SPLIT || p.form == FORM_SPLIT_FOLD;
+    p.fuse_pool = rt.ks_pool && (p.form == FORM_STEM || (p.form == FORM_SPLIT && !g2)) && i + 1 < (int)m->layers.size();
+    p.split_dst = p.form == FORM_PARITY || p.form == FORM_FP32_STEM_SPLIT || p.form == FORM_STEM ||
+                  (on_ks && !L.head && rt.ks->epi != EPI_PLAIN_F32);
+    p.split1 = p.form == FORM_PARITY || on_ks || p.form == FORM_LAST;
+    p.split2 = p.form == FORM_PARITY ? !rt.sphase.ki_skip_stem : on_ks;       // (a 1-channel skip source is read as fp32)
+    p.split_res = on_ks;
+    return p;
+}
+
 // one conv layer on the 2xf16 path: split source (and residual), split output or fused fp32 head
 // (fold: the input of a folded 1x1 projection, split cells -- the layer then runs ks_fold with the projection's channels
 // appended to its K loop, no residual, eval-BN already inside weights and bias)
@@ -158,9 +218,10 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
                    const Slot* fold) {
     const tpz_layer& L = rt.L;
     const SplitKernelInfo& ks = fold ? *rt.ks_fold : pooled ? *rt.ks_pool : *rt.ks;
-    SplitArgs a;
-    memset(&a, 0, sizeof a);
-    a.in = reinterpret_cast<const uint4*>(s1.p);
+    // (a pooled dst is the pooled tensor; the launch covers the un-pooled conv output)
+    const Dhw lat = pooled ? layer_out_dhw(L, dhw(s2 ? *s2 : s1)) : dhw(dst);
+    SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.cout, {dst.D, lat.H, lat.W}, 1, dhw(dst),
+                             L.dims == 3 ? L.k : 0, L.pad, L.slope);
     a.wpk = reinterpret_cast<const uint4*>(fold ? rt.d_wfold : rt.d_wsplit);
     a.wscale = fold ? rt.d_wscale_fold : rt.d_wscale;
     a.bias = bias_view(ctx, fold ? rt.d_bias_fold : rt.d_bias);
@@ -172,36 +233,15 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
     if (L.head) a.head_out = dst.p;
     else if (ks.epi == EPI_PLAIN_F32) a.out_f32 = dst.p;
     else a.out = reinterpret_cast<uint4*>(dst.p);
-    a.zeros = ctx->d_zeros;
-    a.flag = ctx->d_flag;
-    a.slope = L.slope;
-    a.cells_in1 = (int)split_cells(s1.C);
-    a.H1 = s1.H; a.W1 = s1.W;
-    if (s2) {
+    if (s2) {              // fused upsample + concat: s1 nearest-upsampled to the grid of s2
         a.in2 = reinterpret_cast<const uint4*>(s2->p);
         a.cells_in = a.cells_in1 + (int)split_cells(s2->C);
         a.Hin = s2->H; a.Win = s2->W;
-    } else {
-        a.cells_in = a.cells_in1;
-        a.Hin = s1.H; a.Win = s1.W;
     }
-    a.Cout = L.cout;
-    a.cells_out = (int)split_cells(L.cout);
-    a.Hout = dst.H; a.Wout = dst.W;
-    if (pooled) {          // dst is the pooled tensor; the launch covers the un-pooled conv output
-        const Slot& g = s2 ? *s2 : s1;
-        a.Hout = g.H + 2 * L.pad - L.dil * (L.k - 1);
-        a.Wout = g.W + 2 * L.pad - L.dil * (L.k - 1);
-    }
-    a.pad_x = a.pad_y = L.pad;
-    a.os = 1;
-    a.Hfull = dst.H; a.Wfull = dst.W;
     if (sres) { a.Hres = sres->H; a.Wres = sres->W; a.res_crop = L.res_crop; }
+    if (sres && L.dims == 3) a.Dres = sres->D;
     a.n_chunks = rt.s_n_chunks;
     a.cog_inner = L.head ? rt.s_n_cog : 1;
-    if (L.dims == 3) {
-        a.KZ = L.k; a.pad_z = L.pad; a.Din = s1.D; a.Dout = dst.D; a.Dfull = dst.D; a.Dres = sres ? sres->D : 1; a.ooz = 0;
-    }
     double flops = 2.0 * L.cout * L.cin * std::pow((double)L.k, L.dims) * (double)dst.D * a.Hout * a.Wout;
     if (fold) {
         // out(y, x) += proj(h)(y + res_crop, x + res_crop); the centre tap of output y sits at tile-input row y - pad + (k/2) dil
@@ -248,13 +288,7 @@ const SplitStep* split_plan(tpz_ctx* ctx, const SplitKernelInfo& ks, const Split
 }
 
 int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops) {
-    if (a.wy1 < 0) {
-        a.wy1 = -a.wy1;
-        flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
-        if (a.Dlat > 0) flops *= (double)a.Dout / a.Dlat;
-    } else {
-        a.wy0 = a.wx0 = 0; a.wy1 = a.Hout; a.wx1 = a.Wout;
-    }
+    flops = window_flops(a, flops);
     a.tiles_x = (a.wx1 - a.wx0 + ks.TW - 1) / ks.TW;
     a.tiles_y = (a.wy1 - a.wy0 + ks.TH * ks.D - 1) / (ks.TH * ks.D) * ks.D;
     a.xcd_swizzle = 1;
@@ -352,28 +386,15 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
             e = enqueue(ctx, [=](hipStream_t st) { return launch_s2d_split(sp_, X, 1, h1, w1, h2, w2, 2, fl_, st); });
         }
         if (e != hipSuccess) { pool_release(ctx, X); return fail(ctx, "s2d failed: %s", hipGetErrorString(e)); }
-        SplitArgs a;
-        memset(&a, 0, sizeof a);
-        a.in = reinterpret_cast<const uint4*>(s1.p);
+        SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.cout, dhw(s1), 2, dhw(dst), 0, 1, L.slope);
         a.in2 = reinterpret_cast<const uint4*>(X);
+        a.cells_in = a.cells_in1 + 1;
         a.wpk = reinterpret_cast<const uint4*>(sp.d_w_low);
         a.wscale = sp.d_ws_low;
         a.bias = bias_view(ctx, rt.d_bias);
         a.subpix_cout = L.cout;
-        a.pad_x = a.pad_y = 1;
         a.out = reinterpret_cast<uint4*>(dst.p);
-        a.zeros = ctx->d_zeros;
-        a.flag = ctx->d_flag;
-        a.slope = L.slope;
-        a.cells_in1 = (int)split_cells(s1.C);
-        a.cells_in = a.cells_in1 + 1;
-        a.Hin = a.H1 = s1.H; a.Win = a.W1 = s1.W;
-        a.Cout = L.cout; a.cells_out = (int)split_cells(L.cout);
-        a.Hout = s1.H; a.Wout = s1.W;
-        a.os = 2;
-        a.Hfull = dst.H; a.Wfull = dst.W;
         a.n_chunks = sp.n_chunks_low;
-        a.cog_inner = 1;
         const double fl = 2.0 * L.cout * (ph.c1 * 9.0 * 4.0 + 25.0 * 4.0) * (double)s1.H * s1.W;
         set_window(a, dst.need, 2);
         const int rc = launch_split(ctx, *sp.ks_sub, a, sp.n_cog_sub, fl);
@@ -416,39 +437,26 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         const double fl = 2.0 * L.cout * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
         if (launch_mfma(ctx, *sp.ki_skip_stem, a, 1, fl)) return 1;
     } else {
-        SplitArgs a;
-        memset(&a, 0, sizeof a);
-        a.in = reinterpret_cast<const uint4*>(s2.p);
+        SplitArgs a = split_args(ctx, s2.p, (int)split_cells(s2.C), dhw(s2), L.cout, dhw(dst), 1, dhw(dst), L.dims == 3 ? L.k : 0,
+                                 L.pad, 1.f);
         a.wpk = reinterpret_cast<const uint4*>(sp.d_w_skip);
         a.wscale = sp.d_ws_skip;
         a.bias = bias_view(ctx, rt.d_bias);
         a.out = reinterpret_cast<uint4*>(dst.p);
-        a.zeros = ctx->d_zeros;
-        a.flag = ctx->d_flag;
-        a.slope = 1.f;
-        a.cells_in = a.cells_in1 = (int)split_cells(s2.C);
-        a.Hin = a.H1 = s2.H; a.Win = a.W1 = s2.W;
-        a.Cout = L.cout; a.cells_out = (int)split_cells(L.cout);
-        a.Hout = dst.H; a.Wout = dst.W;
-        a.pad_x = a.pad_y = L.pad;
-        a.os = 1; a.Hfull = dst.H; a.Wfull = dst.W;
-        if (L.dims == 3) { a.KZ = L.k; a.pad_z = L.pad; a.Din = s2.D; a.Dout = a.Dfull = dst.D; a.Dres = 1; }
         a.n_chunks = sp.n_chunks_skip;
-        a.cog_inner = 1;
         const double fl = 2.0 * L.cout * ph.c2 * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
         set_window(a, dst.need);       // (even-aligned by need_regions: the parity launch below adds itself in place)
         if (launch_split(ctx, *sp.ks_skip, a, sp.n_cog_skip, fl)) return 1;
     }
     // ---- every output parity over the low-resolution source in one launch, added in place, then the activation
     {
-        SplitArgs a;
-        memset(&a, 0, sizeof a);
-        a.in = reinterpret_cast<const uint4*>(s1.p);
+        // (the lattice of one parity; with nphase set the kernel takes pads and lattice offsets from the parity)
+        SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.cout, dhw(s1), 2, dhw(dst), L.dims == 3 ? ph.k1 : 0,
+                                 sp.ks_sub ? 1 : 0, L.slope);
         a.wpk = reinterpret_cast<const uint4*>(sp.d_w_low);
         a.wscale = sp.d_ws_low;
         if (sp.ks_sub) {
             a.subpix_cout = L.cout;
-            a.pad_x = a.pad_y = 1;
         } else {
             a.nphase = 1 << L.dims;
             a.phase_k = L.k;
@@ -457,27 +465,16 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         }
         a.out = reinterpret_cast<uint4*>(dst.p);
         a.res = reinterpret_cast<const uint4*>(dst.p);
-        a.zeros = ctx->d_zeros;
-        a.flag = ctx->d_flag;
-        a.slope = L.slope;
-        a.cells_in = a.cells_in1 = (int)split_cells(s1.C);
-        if (sp.low_with_skip) {                        // + the space-to-depth cell of the skip source; plain epilogue
+        if (sp.low_with_skip) {                       // + the space-to-depth cell of the skip source; plain epilogue
             a.in2 = reinterpret_cast<const uint4*>(Xs2d);
             a.cells_in = a.cells_in1 + 1;
             a.res = nullptr;
             a.bias = bias_view(ctx, rt.d_bias);
             a.vol_srcmajor = sp.srcmajor ? 1 : 0;
         }
-        a.Hin = a.H1 = s1.H; a.Win = a.W1 = s1.W;
-        a.Cout = L.cout; a.cells_out = (int)split_cells(L.cout);
-        a.Hout = s1.H; a.Wout = s1.W;                  // the lattice of one parity
-        a.os = 2;
-        a.Hfull = dst.H; a.Wfull = dst.W;
-        a.Hres = dst.H; a.Wres = dst.W; a.res_crop = 0;
-        a.KZ = 1; a.Din = a.Dout = a.Dfull = a.Dres = 1;
-        if (L.dims == 3) { a.KZ = ph.k1; a.Din = s1.D; a.Dout = s1.D; a.Dfull = dst.D; a.Dres = dst.D; }
+        a.Hres = dst.H; a.Wres = dst.W;
+        if (L.dims == 3) a.Dres = dst.D;
         a.n_chunks = sp.n_chunks_low;
-        a.cog_inner = 1;
         const double fl = 2.0 * L.cout * ph.c1 * std::pow((double)ph.k1, L.dims) * (double)s1.D * s1.H * s1.W * (1 << L.dims);
         const SplitKernelInfo& kk = sp.ks_sub ? *sp.ks_sub : (sp.low_with_skip ? *sp.ks_low_plain : *sp.ks_low);
         set_window(a, dst.need, 2);
@@ -496,7 +493,7 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
     const int ncell = (L.k + 7) / 8;
     const size_t rows = (size_t)s1.D * s1.H;
     // conv output geometry (dst is the pooled tensor when the max-pool is fused)
-    const int Hc = s1.H + 2 * L.pad - (L.k - 1), Wc = s1.W + 2 * L.pad - (L.k - 1);
+    const int Hc = layer_out_dhw(L, dhw(s1)).H, Wc = layer_out_dhw(L, dhw(s1)).W;      // (dilation 1: prepare_split)
     float* X = (float*)pool_alloc(ctx, (size_t)ncell * 8 * rows * Wc * sizeof(float));
     if (!X) return fail(ctx, "out of device memory");
     // (2-D with a window: only the rows and columns the windowed conv reads -- output row y reads input rows y - pad .. y + pad)
@@ -514,25 +511,14 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
         }
     }
     if (e != hipSuccess) { pool_release(ctx, X); return fail(ctx, "shiftx failed: %s", hipGetErrorString(e)); }
-    SplitArgs a;
-    memset(&a, 0, sizeof a);
-    a.in = reinterpret_cast<const uint4*>(X);
+    SplitArgs a = split_args(ctx, X, ncell, {s1.D, s1.H, Wc}, L.cout, {dst.D, Hc, Wc}, 1, dhw(dst), L.dims == 3 ? L.k : 0, L.pad,
+                             L.slope);
+    a.pad_x = 0;                       // (the kx taps are channels of X)
     a.wpk = reinterpret_cast<const uint4*>(rt.d_wsplit);
     a.wscale = rt.d_wscale;
     a.bias = bias_view(ctx, rt.d_bias);
     a.out = reinterpret_cast<uint4*>(dst.p);
-    a.zeros = ctx->d_zeros;
-    a.flag = ctx->d_flag;
-    a.slope = L.slope;
-    a.cells_in = a.cells_in1 = ncell;
-    a.Hin = a.H1 = s1.H; a.Win = a.W1 = Wc;
-    a.Cout = L.cout; a.cells_out = (int)split_cells(L.cout);
-    a.Hout = Hc; a.Wout = Wc;
-    a.pad_x = 0; a.pad_y = L.pad;
-    a.os = 1; a.Hfull = dst.H; a.Wfull = dst.W;
-    if (L.dims == 3) { a.KZ = L.k; a.pad_z = L.pad; a.Din = s1.D; a.Dout = a.Dfull = dst.D; a.Dres = 1; }
     a.n_chunks = rt.s_n_chunks;
-    a.cog_inner = 1;
     const double fl = 2.0 * L.cout * std::pow((double)L.k, L.dims) * (double)dst.D * Hc * Wc;
     set_window(a, dst.need);
     const int rc = launch_split(ctx, ks, a, rt.s_n_cog, fl);
@@ -575,24 +561,13 @@ int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, c
     const size_t rows = (size_t)dst.D * dst.H;
     float* Y = (float*)pool_alloc(ctx, (size_t)L.k * rows * Wp * sizeof(float));
     if (!Y) return fail(ctx, "out of device memory");
-    SplitArgs a;
-    memset(&a, 0, sizeof a);
-    a.in = reinterpret_cast<const uint4*>(s1.p);
+    const Dhw lat = {dst.D, dst.H, Wp};
+    SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.k, lat, 1, lat, L.dims == 3 ? L.k : 0, L.pad, 1.f);
+    a.cells_out = 1;
     a.wpk = reinterpret_cast<const uint4*>(rt.d_wsplit);
     a.wscale = rt.d_wscale;
     a.out_f32 = Y;
-    a.zeros = ctx->d_zeros;
-    a.flag = ctx->d_flag;
-    a.slope = 1.f;
-    a.cells_in = a.cells_in1 = (int)split_cells(s1.C);
-    a.Hin = a.H1 = s1.H; a.Win = a.W1 = s1.W;
-    a.Cout = L.k; a.cells_out = 1;
-    a.Hout = dst.H; a.Wout = Wp;
-    a.pad_x = a.pad_y = L.pad;
-    a.os = 1; a.Hfull = dst.H; a.Wfull = Wp;
-    if (L.dims == 3) { a.KZ = L.k; a.pad_z = L.pad; a.Din = s1.D; a.Dout = a.Dfull = dst.D; a.Dres = 1; }
     a.n_chunks = rt.s_n_chunks;
-    a.cog_inner = 1;
     const double fl = 2.0 * L.cin * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
     const Rect& w = dst.need;
     set_window(a, w, 1, 2 * L.pad);       // Y columns x .. x + k - 1 feed output column x
@@ -712,6 +687,24 @@ int nearest_src_host(int dst, int in_sz, int out_sz) {
     return v < in_sz - 1 ? v : in_sz - 1;
 }
 
+// May a layer that conv_plan gives this form compute just a window of its tensor in a 2xf16 pass?  The 2xf16 forms may.  The fp32
+// forms may not: the format conversions either side of them read whole tensors, and what a windowed producer did not write may
+// hold any bit pattern (the overflow flag).  Three named conditions depart from that rule; each is an open question, not a design:
+bool form_windowable(ConvForm form, const LayerRT& rt, int dims) {
+    // a column-kernel stem that reads a 1-channel tensor other than the input leaves its program whole (no model of the
+    // package has one; the form itself windows like any other)
+    const bool stem_off_input = form == FORM_STEM && rt.L.src != 0;
+    // so does a 2-D per-parity layer with a 1-channel skip source that has no fused-loader kernel (rt.ks) beside it -- although
+    // every launch of the form covers its window or the whole grid, and the same form is windowed in 3-D
+    const bool parity_2d_image_skip = form == FORM_PARITY && dims == 2 && rt.sphase.ki_skip_stem && !rt.ks;
+    // a 2-D decoder layer with per-parity kernels over a multi-channel skip source whose shapes are not exactly 2x and which has
+    // no rt.ks runs on its fp32 kernel, between format conversions, and its program IS windowed: the case the rule above forbids
+    const bool inexact_2d_decoder_on_fp32 = form == FORM_FP32 && dims == 2 && rt.sphase.valid && !rt.sphase.ki_skip_stem;
+    if (stem_off_input || parity_2d_image_skip) return false;
+    return form == FORM_SPLIT || form == FORM_SPLIT_FOLD || form == FORM_STEM || form == FORM_LAST || form == FORM_PARITY ||
+           inexact_2d_decoder_on_fp32;
+}
+
 // Which part of every slot's tensor do the pixels `keep` of the program's output depend on?  (2-D programs, on the 2xf16
 // kernels or -- exact mode -- on the fp32 kernels, whose launches take the same windows: ConvArgs::wy0..wx1.)  A patched denoise keeps only the centre of each patch (denoise.py:299-323: patch_size pixels of a patch_size +
 // 2*padding tile; CLI default 1024 of 2024), and the U-Net's receptive field (~230 pixels) is far smaller than the default
@@ -741,35 +734,29 @@ std::vector<Rect> need_regions(const tpz_model* m, int D0, int H0, int W0, const
     // re-run of a tiled tomogram no longer compute every tile in full)
     // shapes of all slots
     std::vector<int> Ds(m->n_slots, 1), Hs(m->n_slots, 0), Ws(m->n_slots, 0);
-    Ds[0] = D0; Hs[0] = H0; Ws[0] = W0;
+    std::vector<char> fmt(m->n_slots, 0), set(m->n_slots, 0);      // ... their format (1: split cells), as run_program will leave it
+    Ds[0] = D0; Hs[0] = H0; Ws[0] = W0; set[0] = 1;
+    auto shape = [&](int s) { return Dhw{Ds[s], Hs[s], Ws[s]}; };
     for (int i = 0; i < nl; ++i) {
         const LayerRT& rt = m->layers[i];
         const tpz_layer& L = rt.L;
-        if (L.dims != dims || (split && rt.folded_into >= 0)) return bail(2);
+        if (L.dims != dims) return bail(2);
+        const int g = (L.op == TPZ_OP_CONV && L.src2 >= 0) ? L.src2 : L.src;
         if (L.op == TPZ_OP_CONV) {
-            // (a 2xf16 program with a layer left on an fp32 kernel stays whole: the format conversions between the two read
-            // whole tensors, and what a windowed producer did not write may hold any bit pattern -- the overflow flag)
-            const int g = L.src2 >= 0 ? L.src2 : L.src, span = L.dil * (L.k - 1);
-            // (the per-parity form runs when the skip source is exactly twice the upsampled one -- run_program's rule; with a
-            // 1-channel skip source it either takes that source as a space-to-depth cell or runs it through the fp32 stem kernel
-            // over the whole grid, which reads only the image)
-            const bool parity = rt.sphase.valid && L.src2 >= 0 && Hs[g] == 2 * Hs[L.src] && Ws[g] == 2 * Ws[L.src] &&
-                                (dims == 2 || Ds[g] == 2 * Ds[L.src]);
-            const bool own = rt.ks || rt.ks_last || (rt.ks_stem && L.src == 0);
-            const bool windowed = dims == 3 ? (own || parity) : (own || (rt.sphase.valid && !rt.sphase.ki_skip_stem));
-            if (split && !windowed) return bail(3);
-            Hs[L.dst] = Hs[g] + 2 * L.pad - span; Ws[L.dst] = Ws[g] + 2 * L.pad - span;
-            if (dims == 3) Ds[L.dst] = Ds[g] + 2 * L.pad - span;
-        } else if (L.op == TPZ_OP_MAXPOOL2) {
-            Hs[L.dst] = Hs[L.src] / 2; Ws[L.dst] = Ws[L.src] / 2;
-            if (dims == 3) Ds[L.dst] = Ds[L.src] / 2;
-        } else if (L.op == TPZ_OP_MAXPOOL) {
-            Hs[L.dst] = Hs[L.src] - L.dil * (L.k - 1); Ws[L.dst] = Ws[L.src] - L.dil * (L.k - 1);
-            if (dims == 3) Ds[L.dst] = Ds[L.src] - L.dil * (L.k - 1);
+            const Dhw g2 = shape(g);
+            const ConvPlan pl = conv_plan(m, i, split, shape(L.src), L.src2 >= 0 ? &g2 : nullptr, fmt[L.src] != 0,
+                                          rt.fold_src >= 0 && set[rt.fold_src]);
+            if (pl.form == FORM_FOLDED_AWAY) return bail(2);
+            if (split && !form_windowable(pl.form, rt, dims)) return bail(3);
+            fmt[L.dst] = pl.split_dst;
+        } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL) {
+            fmt[L.dst] = fmt[L.src] && i != nl - 1;                // pooled in the format the source has
         } else {
             return bail(4);
         }
-        if (Ds[L.dst] < 1 || Hs[L.dst] < 1 || Ws[L.dst] < 1) return bail(5);
+        const Dhw o = layer_out_dhw(L, shape(g));
+        Ds[L.dst] = o.D; Hs[L.dst] = o.H; Ws[L.dst] = o.W; set[L.dst] = 1;
+        if (o.D < 1 || o.H < 1 || o.W < 1) return bail(5);
     }
     need.assign(m->n_slots, Rect());
     // (2-D: every box is the one plane [0, 1))
@@ -851,84 +838,79 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
         const Slot& s1 = slots[L.src];
         if (!s1.set) { rc = fail(ctx, "layer %d reads unset slot %d", i, L.src); break; }
         Slot& dst = slots[L.dst];
-        if (L.op == TPZ_OP_CONV && split && rt.folded_into >= 0 && m->layers[rt.folded_into].ks_fold) {
+        const bool last = i == nl - 1;
+        const Slot* s2 = (L.op == TPZ_OP_CONV && L.src2 >= 0) ? &slots[L.src2] : nullptr;
+        const Dhw g2 = s2 ? dhw(*s2) : Dhw();
+        // which kernels run a conv layer, and in which formats: conv_plan's decision, dispatched below
+        const ConvPlan pl = L.op == TPZ_OP_CONV ? conv_plan(m, i, split, dhw(s1), s2 ? &g2 : nullptr, s1.split,
+                                                            rt.fold_src >= 0 && slots[rt.fold_src].set) : ConvPlan();
+        if (pl.form == FORM_FOLDED_AWAY) {
             // a 1x1 projection folded into the conv that adds it (prepare_split): nothing to run, its slot stays unset
         } else if (L.op == TPZ_OP_CONV) {
-            const bool fold_here = split && rt.ks_fold && rt.fold_src >= 0 && slots[rt.fold_src].set;
-            const Slot* s2 = L.src2 >= 0 ? &slots[L.src2] : nullptr;
-            const Slot* sres = (L.res >= 0 && !fold_here) ? &slots[L.res] : nullptr;
+            const Slot* sres = (L.res >= 0 && pl.form != FORM_SPLIT_FOLD) ? &slots[L.res] : nullptr;
             if ((s2 && !s2->set) || (sres && !sres->set)) { rc = fail(ctx, "layer %d reads an unset slot", i); break; }
             const Slot& geo = s2 ? *s2 : s1;
             if (s1.C + (s2 ? s2->C : 0) != L.cin) {
                 rc = fail(ctx, "layer %d: cin %d != channels of its sources (%d)", i, L.cin, s1.C + (s2 ? s2->C : 0));
                 break;
             }
-            const int span = L.dil * (L.k - 1);
-            const int Do = L.dims == 3 ? geo.D + 2 * L.pad - span : 1;
-            const int Ho = geo.H + 2 * L.pad - span, Wo = geo.W + 2 * L.pad - span;
-            if (Do < 1 || Ho < 1 || Wo < 1) { rc = fail(ctx, "layer %d: input %dx%dx%d too small", i, geo.D, geo.H, geo.W); break; }
+            const Dhw o = layer_out_dhw(L, dhw(geo));
+            if (o.D < 1 || o.H < 1 || o.W < 1) { rc = fail(ctx, "layer %d: input %dx%dx%d too small", i, geo.D, geo.H, geo.W); break; }
             const int Co = L.head ? 1 : L.cout;
-            if (sres && (sres->H - 2 * L.res_crop != Ho || sres->W - 2 * L.res_crop != Wo || sres->C != L.cout)) {
+            if (sres && (sres->H - 2 * L.res_crop != o.H || sres->W - 2 * L.res_crop != o.W || sres->C != L.cout)) {
                 rc = fail(ctx, "layer %d: residual geometry mismatch", i);
                 break;
             }
-            // which kernels run the layer: the 2xf16 per-parity twin, a 2xf16 kernel, or the fp32 path
-            const bool exact2x = s2 && s2->H == 2 * s1.H && s2->W == 2 * s1.W && (L.dims == 2 || s2->D == 2 * s1.D);
-            const bool use_sphase = split && rt.sphase.valid && exact2x;
-            const bool use_split = split && rt.ks && !use_sphase;      // (fold_here implies it)
-            const bool use_stem = split && rt.ks_stem && !s1.split;
-            const bool use_last = split && rt.ks_last;
-            const bool stem_split = split && !use_sphase && !use_split && !use_stem && rt.ki_stem_split;
-            const bool split_dst = use_sphase || stem_split || use_stem || (use_split && !L.head && rt.ks->epi != EPI_PLAIN_F32);
-            // the max-pool that follows is applied in this conv's epilogue: the slot receives the pooled tensor
-            const bool fuse_pool = rt.ks_pool && (use_stem || (use_split && !s2)) && i + 1 < nl;
-            const int Hd = fuse_pool ? Ho / 2 : Ho, Wd = fuse_pool ? Wo / 2 : Wo;
+            // a fused max-pool: the slot receives the pooled tensor
+            const int Hd = pl.fuse_pool ? o.H / 2 : o.H, Wd = pl.fuse_pool ? o.W / 2 : o.W;
             // split tensors take the bytes of fp32 with the channels rounded up to whole 8-channel cells
-            const size_t c_alloc = split_dst ? split_cells(Co) * 8 : (size_t)Co;
-            float* p = (i == nl - 1) ? d_out : (float*)pool_alloc(ctx, c_alloc * Do * Hd * Wd * sizeof(float));
+            const size_t c_alloc = pl.split_dst ? split_cells(Co) * 8 : (size_t)Co;
+            float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * Hd * Wd * sizeof(float));
             if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
-            if (fuse_pool && (Hd < 1 || Wd < 1)) { rc = fail(ctx, "layer %d: input too small to pool", i + 1); break; }
-            set_dense(dst, p, Co, Do, Hd, Wd);
+            if (pl.fuse_pool && (Hd < 1 || Wd < 1)) { rc = fail(ctx, "layer %d: input too small to pool", i + 1); break; }
+            set_dense(dst, p, Co, o.D, Hd, Wd);
             dst.need = need.empty() ? Rect() : need[L.dst];
-            dst.split = split_dst;
-            dst.pooled = fuse_pool;
+            dst.split = pl.split_dst;
+            dst.pooled = pl.fuse_pool;
             dst.alt = nullptr;
-            dst.owned = (i != nl - 1);
-            if (split_dst && i == nl - 1) { rc = fail(ctx, "layer %d: the result must leave as fp32", i); break; }
+            dst.owned = !last;
+            if (pl.split_dst && last) { rc = fail(ctx, "layer %d: the result must leave as fp32", i); break; }
             // sources in the format the chosen kernels read (converted once if the producer wrote the other one)
-            const bool want1 = use_sphase || use_split || use_last;
-            const bool want2 = use_sphase ? !rt.sphase.ki_skip_stem : use_split;
             Slot v1 = s1, v2, vres;
-            v1.p = slot_as(ctx, slots[L.src], want1);
-            v1.split = want1;
-            if (s2) { v2 = *s2; v2.p = slot_as(ctx, slots[L.src2], want2); v2.split = want2; }
-            if (sres) { vres = *sres; vres.p = slot_as(ctx, slots[L.res], use_split && !use_last); vres.split = use_split && !use_last; }
+            v1.p = slot_as(ctx, slots[L.src], pl.split1);
+            v1.split = pl.split1;
+            if (s2) { v2 = *s2; v2.p = slot_as(ctx, slots[L.src2], pl.split2); v2.split = pl.split2; }
+            if (sres) { vres = *sres; vres.p = slot_as(ctx, slots[L.res], pl.split_res); vres.split = pl.split_res; }
             if (!v1.p || (s2 && !v2.p) || (sres && !vres.p)) { rc = fail(ctx, "layer %d: tensor format conversion failed", i); break; }
             // slot 0 arrives already normalised (denoise_region); only the last layer un-normalises
-            if (use_stem) rc = run_stem_split(ctx, rt, v1, dst, fuse_pool);
-            else if (use_last) rc = run_last_split(ctx, rt, v1, dst, d_nrm, (d_nrm && i == nl - 1) ? 1 : 0, sres ? &vres : nullptr);
-            else if (use_sphase) rc = run_conv_split_phases(ctx, rt, v1, v2, dst);
-            else if (use_split && fold_here) {
+            const int norm_out = (d_nrm && last) ? 1 : 0;
+            switch (pl.form) {
+            case FORM_STEM: rc = run_stem_split(ctx, rt, v1, dst, pl.fuse_pool); break;
+            case FORM_LAST: rc = run_last_split(ctx, rt, v1, dst, d_nrm, norm_out, sres ? &vres : nullptr); break;
+            case FORM_PARITY: rc = run_conv_split_phases(ctx, rt, v1, v2, dst); break;
+            case FORM_SPLIT_FOLD: {
                 Slot vf = slots[rt.fold_src];
                 vf.p = slot_as(ctx, slots[rt.fold_src], true);
                 vf.split = true;
-                if (!vf.p) { rc = fail(ctx, "layer %d: tensor format conversion failed", i); break; }
-                rc = run_conv_split(ctx, rt, v1, nullptr, dst, nullptr, false, &vf);
+                if (!vf.p) rc = fail(ctx, "layer %d: tensor format conversion failed", i);
+                else rc = run_conv_split(ctx, rt, v1, nullptr, dst, nullptr, false, &vf);
+                break;
             }
-            else if (use_split) rc = run_conv_split(ctx, rt, v1, sres ? &vres : nullptr, dst, s2 ? &v2 : nullptr, fuse_pool);
-            else rc = run_conv(ctx, rt, v1, s2 ? &v2 : nullptr, sres ? &vres : nullptr, dst, d_nrm,
-                               (d_nrm && i == nl - 1) ? 1 : 0, stem_split);
+            case FORM_SPLIT: rc = run_conv_split(ctx, rt, v1, sres ? &vres : nullptr, dst, s2 ? &v2 : nullptr, pl.fuse_pool); break;
+            default: rc = run_conv(ctx, rt, v1, s2 ? &v2 : nullptr, sres ? &vres : nullptr, dst, d_nrm, norm_out,
+                                   pl.form == FORM_FP32_STEM_SPLIT);
+            }
         } else if (L.op == TPZ_OP_MAXPOOL2 && s1.pooled && L.dims == 3) {
             // pooled in-plane by the producing conv: the z pairs remain
             const int Do = s1.D / 2;
             if (Do < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
-            float* p = (i == nl - 1) ? d_out : (float*)pool_alloc(ctx, split_cells(s1.C) * 8 * (size_t)Do * s1.H * s1.W * sizeof(float));
+            float* p = last ? d_out : (float*)pool_alloc(ctx, split_cells(s1.C) * 8 * (size_t)Do * s1.H * s1.W * sizeof(float));
             if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
             const Slot src = s1;
             set_dense(dst, p, src.C, Do, src.H, src.W);
             dst.split = true;
             dst.alt = nullptr;
-            dst.owned = (i != nl - 1);
+            dst.owned = !last;
             hipError_t e;
             {
                 const float* sp_ = src.p; float* dp_ = dst.p;
@@ -943,52 +925,28 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             dst.pooled = false;
             slots[L.src].owned = false;
             slots[L.src].alt = nullptr;
-        } else if (L.op == TPZ_OP_MAXPOOL2) {
+        } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL) {
             if (s1.pitch != s1.W || s1.ps != (long long)s1.H * s1.W) { rc = fail(ctx, "maxpool needs a dense input"); break; }
-            const int Do = L.dims == 3 ? s1.D / 2 : 1, Ho = s1.H / 2, Wo = s1.W / 2;
-            if (Do < 1 || Ho < 1 || Wo < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
-            const bool sp = s1.split && i != nl - 1;          // pooled in the format the source has
+            const Dhw o = layer_out_dhw(L, dhw(s1));
+            if (o.D < 1 || o.H < 1 || o.W < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
+            const bool sp = s1.split && !last;                // pooled in the format the source has
             const float* src_p = s1.p;
             if (s1.split && !sp) { src_p = slot_as(ctx, slots[L.src], false); if (!src_p) { rc = fail(ctx, "conversion failed"); break; } }
             const size_t c_alloc = sp ? split_cells(s1.C) * 8 : (size_t)s1.C;
-            float* p = (i == nl - 1) ? d_out : (float*)pool_alloc(ctx, c_alloc * Do * Ho * Wo * sizeof(float));
+            float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * o.H * o.W * sizeof(float));
             if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
             const int Cs = s1.C, Ds = s1.D, Hs = s1.H, Ws = s1.W;
-            set_dense(dst, p, Cs, Do, Ho, Wo);
+            set_dense(dst, p, Cs, o.D, o.H, o.W);
             dst.split = sp;
             dst.alt = nullptr;
-            dst.owned = (i != nl - 1);
-            hipError_t e;
-            {
-                float* dp_ = dst.p;
-                const int dims = L.dims;
-                e = enqueue(ctx, [=](hipStream_t st) {
-                    return sp ? launch_maxpool2_split(src_p, dp_, Cs, Ds, Hs, Ws, dims, st) : launch_maxpool2(src_p, dp_, Cs, Ds, Hs, Ws, dims, st);
-                });
-            }
-            if (e != hipSuccess) rc = fail(ctx, "maxpool launch failed: %s", hipGetErrorString(e));
-        } else if (L.op == TPZ_OP_MAXPOOL) {
-            if (s1.pitch != s1.W || s1.ps != (long long)s1.H * s1.W) { rc = fail(ctx, "maxpool needs a dense input"); break; }
-            const int span = L.dil * (L.k - 1);
-            const int Do = L.dims == 3 ? s1.D - span : 1, Ho = s1.H - span, Wo = s1.W - span;
-            if (Do < 1 || Ho < 1 || Wo < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
-            const bool sp = s1.split && i != nl - 1;          // pooled in the format the source has
-            const float* src_p = s1.p;
-            if (s1.split && !sp) { src_p = slot_as(ctx, slots[L.src], false); if (!src_p) { rc = fail(ctx, "conversion failed"); break; } }
-            const size_t c_alloc = sp ? split_cells(s1.C) * 8 : (size_t)s1.C;
-            float* p = (i == nl - 1) ? d_out : (float*)pool_alloc(ctx, c_alloc * Do * Ho * Wo * sizeof(float));
-            if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
-            const int Cs = s1.C, Ds = s1.D, Hs = s1.H, Ws = s1.W;
-            set_dense(dst, p, Cs, Do, Ho, Wo);
-            dst.split = sp;
-            dst.alt = nullptr;
-            dst.owned = (i != nl - 1);
-            hipError_t e;
-            {
-                float* dp_ = dst.p;
-                const int k = L.k, dil = L.dil, dims = L.dims;
-                e = enqueue(ctx, [=](hipStream_t st) { return launch_maxpoolk(src_p, dp_, Cs, Ds, Hs, Ws, k, dil, dims, sp, st); });
-            }
+            dst.owned = !last;
+            float* dp_ = dst.p;
+            const int k = L.k, dil = L.dil, dims = L.dims;
+            const bool by2 = L.op == TPZ_OP_MAXPOOL2;
+            const hipError_t e = enqueue(ctx, [=](hipStream_t st) {
+                if (!by2) return launch_maxpoolk(src_p, dp_, Cs, Ds, Hs, Ws, k, dil, dims, sp, st);
+                return sp ? launch_maxpool2_split(src_p, dp_, Cs, Ds, Hs, Ws, dims, st) : launch_maxpool2(src_p, dp_, Cs, Ds, Hs, Ws, dims, st);
+            });
             if (e != hipSuccess) rc = fail(ctx, "maxpool launch failed: %s", hipGetErrorString(e));
         } else {
             rc = fail(ctx, "layer %d: unknown op %d", i, L.op);

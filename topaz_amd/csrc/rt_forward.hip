@@ -167,9 +167,7 @@ int tpz_conv_split_2d(tpz_ctx* ctx, const float* d_in, int cin, int H, int W, co
     std::vector<uint16_t> packed;
     std::vector<float> inv;
     pack_weights_split(*rt.ks, h_w, cout, cin, rt.s_n_cog, rt.s_n_chunks, packed, inv);
-    float* d = nullptr;
-    int rc = upload(ctx, &tmp, reinterpret_cast<const float*>(packed.data()), (packed.size() + 1) / 2, &d);
-    rt.d_wsplit = d;
+    int rc = upload_halfs(ctx, &tmp, packed, &rt.d_wsplit);
     if (!rc) rc = upload_chan(ctx, &tmp, inv.data(), inv.size(), &rt.d_wscale);
     if (!rc && h_b) rc = upload_chan(ctx, &tmp, h_b, cout, &rt.d_bias);
     if (!rc && h_post_scale) rc = upload_chan(ctx, &tmp, h_post_scale, cout, &rt.d_post_scale);

@@ -5,9 +5,11 @@
 // The runtime is split into translation units by concern:
 //   rt_core.hip     kernel registries, the context (streams, workspace pools, patch lanes, the batched-launch recorder, the
 //                   HIP-event profiler), its setters, the debug switches
-//   rt_load.hip     model loading: kernel choice per layer, weight packing (fp32 and 2xf16 forms), per-parity decoder forms,
-//                   folded projections, zero-padded widths, the bias arena
-//   rt_exec.hip     the layer-program executor: launchers, per-layer drivers, the backward walk of the windows (need_regions)
+//   rt_load.hip     model loading: the kernels each layer CAN run on and their weight packs (fp32 and 2xf16 forms, per-parity
+//                   decoder forms, folded projections), zero-padded widths, the bias arena
+//   rt_exec.hip     the layer-program executor: conv_plan() -- the one place that says which of those kernels a conv layer
+//                   DOES run on, in which tensor formats (ConvForm / ConvPlan below) --, launchers, per-layer drivers, the
+//                   backward walk of the windows (need_regions)
 //   rt_forward.hip  scoring drivers (range-scaled pass, internal tiling) and the single-op entry points
 //   rt_denoise.hip  the patched 2-D and tiled 3-D denoising drivers (batched passes over the lanes)
 //   rt_stats.hip    mean / std, GMM fit, affine, normalise
@@ -370,12 +372,42 @@ static void set_dense(Slot& s, float* p, int C, int D, int H, int W) {
 // a bias-like vector as the current pass reads it (the scaled copy in a range-scaled pass)
 static inline const float* bias_view(const tpz_ctx* ctx, const float* p) { return p ? p + ctx->bias_shift : nullptr; }
 
+// ---- which kernels run conv layer i, and in which tensor format: decided by conv_plan() and nowhere else ----------------------
+// The loader (rt_load.hip prepare_split) equips a layer with the 2xf16 forms it has kernels for; conv_plan() picks the one a run
+// takes from the shapes and formats it meets.  run_program dispatches on the result, need_regions asks form_windowable() about
+// it, and the coverage count of the loader asks split_forms() whether there is any.
+enum ConvForm {
+    FORM_FP32,             // fp32 MFMA kernel (rt.ki; its per-parity form where the shapes allow, run_conv) or the direct kernel
+    FORM_FP32_STEM_SPLIT,  // the fp32 1-channel stem storing split cells (rt.ki_stem_split)
+    FORM_SPLIT,            // 2xf16 kernel (rt.ks; rt.ks_pool with fuse_pool; the weights-resident kernel where run_conv_split may)
+    FORM_SPLIT_FOLD,       // 2xf16 kernel with a 1x1 projection folded into its K loop (rt.ks_fold)
+    FORM_STEM,             // 1-channel stem as a column kernel over an x-shifted copy of the image (rt.ks_stem)
+    FORM_LAST,             // 1-output-channel last conv (rt.ks_last): the vector-ALU stencil (rt.d_wlast) or column kernel + shift-sum
+    FORM_PARITY,           // decoder conv over an exactly 2x upsampled + a skip source, by output parity (rt.sphase)
+    FORM_FOLDED_AWAY,      // a 1x1 projection absorbed into the conv that adds it (rt.folded_into): nothing runs
+};
+struct ConvPlan {
+    ConvForm form = FORM_FP32;
+    bool fuse_pool = false;      // the 2x2 max-pool that follows runs in this conv's epilogue: the slot receives the pooled tensor
+    bool split_dst = false;      // the destination holds split cells
+    bool split1 = false, split2 = false, split_res = false;      // the format source 1, source 2 and the residual are read in
+};
+struct Dhw { int D = 1, H = 0, W = 0; };
+
+// output size of a layer (conv, MAXPOOL, MAXPOOL2) from its geometry source: the second source of a conv that has one, else the first
+static inline Dhw layer_out_dhw(const tpz_layer& L, const Dhw& g) {
+    if (L.op != TPZ_OP_CONV && L.op != TPZ_OP_MAXPOOL) return {L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};
+    const int grow = (L.op == TPZ_OP_CONV ? 2 * L.pad : 0) - L.dil * (L.k - 1);
+    return {L.dims == 3 ? g.D + grow : 1, g.H + grow, g.W + grow};
+}
+
 // ---- cross-TU functions (defined in the file named)
 // rt_load.hip
 static inline size_t chan_pad(size_t n) { return (n + 127) / 128 * 128 + 128; }     // per-channel vectors: whole 128-channel tiles + one
 static inline int phase_pad(int k, int p) { return (k / 2 - p + 1) / 2; }
 int upload(tpz_ctx* ctx, tpz_model* m, const float* h, size_t n, float** out);
 int upload_chan(tpz_ctx* ctx, tpz_model* m, const float* h, size_t n, float** out);
+int upload_halfs(tpz_ctx* ctx, tpz_model* m, const std::vector<uint16_t>& h, void** out);      // packed f16 weights
 void pack_weights_split(const SplitKernelInfo& ki, const float* w, int cout, int cin, int n_cog, int n_chunks,
                         std::vector<uint16_t>& out, std::vector<float>& wscale_inv, const float* wp = nullptr, int cin_b = 0,
                         const float* mul = nullptr);
@@ -383,6 +415,9 @@ const SplitKernelInfo* pick_split(int k, int dil, int cout, int epi, int kx = 0)
 int model_load(tpz_ctx* ctx, const tpz_layer* layers, int n_layers, const float* h_blob, size_t n_floats,
                const std::vector<int>& preset_chan, tpz_model** out);
 // rt_exec.hip
+unsigned split_forms(const tpz_model* m, int i);       // the 2xf16 forms layer i was loaded with: bit (1 << ConvForm) each
+// g1 / g2: D, H, W of the sources (g2 = nullptr: one source); split1: source 1 holds split cells; fold_set: rt.fold_src is set
+ConvPlan conv_plan(const tpz_model* m, int i, bool split, const Dhw& g1, const Dhw* g2, bool split1, bool fold_set);
 int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* sres, Slot& dst, const Slot* s2 = nullptr,
                    bool pooled = false, const Slot* fold = nullptr);
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split = false,

@@ -22,14 +22,13 @@ int upload_chan(tpz_ctx* ctx, tpz_model* m, const float* h, size_t n, float** ou
 
 namespace {
 
-const int MT_CHOICES[] = {16, 32, 48, 64, 96, 128};
-
-// choose the MFMA instantiation for a conv layer; returns nullptr when the direct kernel must be used
-const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool cin1, int epi) {
-    const ConvKernelInfo* best = nullptr;
+// of the instantiations find(mt) compiled for the tile widths mt, the one that pads cout the least (ties: the wider tile)
+template <class Find>
+auto pick_by_padded_width(int cout, Find find) -> decltype(find(0)) {
+    decltype(find(0)) best = nullptr;
     int best_padded = 1 << 30;
-    for (int mt : MT_CHOICES) {
-        const ConvKernelInfo* c = find_conv(dims, k, dil, mt, cin1, epi);
+    for (int mt : {16, 32, 48, 64, 96, 128}) {
+        const auto c = find(mt);
         if (!c) continue;
         const int padded = (cout + mt - 1) / mt * mt;
         if (padded < best_padded || (padded == best_padded && best && mt > best->MT)) {
@@ -38,6 +37,11 @@ const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool cin1, i
         }
     }
     return best;
+}
+
+// choose the MFMA instantiation for a conv layer; returns nullptr when the direct kernel must be used
+const ConvKernelInfo* pick_conv(int dims, int k, int dil, int cout, bool cin1, int epi) {
+    return pick_by_padded_width(cout, [&](int mt) { return find_conv(dims, k, dil, mt, cin1, epi); });
 }
 
 const ConvKernelInfo* choose_kernel(const tpz_layer& L) {
@@ -103,6 +107,32 @@ int phase_tap(int k, int p, int ky) {
     return (v >= 0 ? v / 2 : -((-v + 1) / 2)) + phase_pad(k, p);
 }
 
+// the k1-tap weights [cout][c1][k1 (3-D)][k1][k1] of output parity p over the low-resolution source: sums of the original taps
+void phase_weights(const tpz_layer& L, const float* w, int c1, int p, std::vector<double>& acc) {
+    const int k = L.k, k1 = k / 2 + 1, kz_n = L.dims == 3 ? k : 1;
+    const size_t taps = (size_t)kz_n * k * k, taps1 = (size_t)(L.dims == 3 ? k1 : 1) * k1 * k1;
+    const int px = p & 1, py = (p >> 1) & 1, pz = L.dims == 3 ? (p >> 2) & 1 : 0;
+    acc.assign((size_t)L.cout * c1 * taps1, 0.0);
+    for (int co = 0; co < L.cout; ++co)
+        for (int ci = 0; ci < c1; ++ci)
+            for (int kz = 0; kz < kz_n; ++kz)
+                for (int ky = 0; ky < k; ++ky)
+                    for (int kx = 0; kx < k; ++kx) {
+                        const int tz = L.dims == 3 ? phase_tap(k, pz, kz) : 0;
+                        acc[((size_t)co * c1 + ci) * taps1 + ((size_t)tz * k1 + phase_tap(k, py, ky)) * k1 + phase_tap(k, px, kx)] +=
+                            (double)w[((size_t)co * L.cin + ci) * taps + ((size_t)kz * k + ky) * k + kx];
+                    }
+}
+
+// the weights [cout][c2][taps] of the skip source: input channels c1 .. c1 + c2 - 1 of the layer
+void skip_weights(const tpz_layer& L, const float* w, int c1, int c2, std::vector<float>& eff) {
+    const size_t taps = L.dims == 3 ? (size_t)L.k * L.k * L.k : (size_t)L.k * L.k;
+    eff.resize((size_t)L.cout * c2 * taps);
+    for (int co = 0; co < L.cout; ++co)
+        for (int ci = 0; ci < c2; ++ci)
+            memcpy(&eff[((size_t)co * c2 + ci) * taps], &w[((size_t)co * L.cin + c1 + ci) * taps], taps * sizeof(float));
+}
+
 int prepare_phases(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* w, int c1, int c2, LayerRT& rt) {
     LayerRT::Phase& ph = rt.phase;
     if (L.src2 < 0 || L.dil != 1 || (L.k != 3 && L.k != 5) || L.pad != L.k / 2 || L.res >= 0 || L.head ||
@@ -113,37 +143,19 @@ int prepare_phases(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* 
     ph.ki_skip = pick_conv(dims, k, 1, L.cout, c2 == 1, EPI_RES);
     if (!ph.ki_low || !ph.ki_skip) return 0;
     ph.c1 = c1; ph.c2 = c2; ph.k1 = k1;
-    const int kz_n = dims == 3 ? k : 1, k1z_n = dims == 3 ? k1 : 1;
-    const size_t taps = (size_t)kz_n * k * k, taps1 = (size_t)k1z_n * k1 * k1;
     ph.n_cog_low = (L.cout + ph.ki_low->MT - 1) / ph.ki_low->MT;
     ph.n_chunks_low = (c1 + ph.ki_low->NCH - 1) / ph.ki_low->NCH;
     ph.n_cog_skip = (L.cout + ph.ki_skip->MT - 1) / ph.ki_skip->MT;
     ph.n_chunks_skip = ph.ki_skip->cin1 ? 1 : (c2 + ph.ki_skip->NCH - 1) / ph.ki_skip->NCH;
     std::vector<double> acc;
     std::vector<float> eff, packed;
-    const int n_phase = 1 << dims;
-    for (int p = 0; p < n_phase; ++p) {
-        const int px = p & 1, py = (p >> 1) & 1, pz = dims == 3 ? (p >> 2) & 1 : 0;
-        acc.assign((size_t)L.cout * c1 * taps1, 0.0);
-        for (int co = 0; co < L.cout; ++co)
-            for (int ci = 0; ci < c1; ++ci)
-                for (int kz = 0; kz < kz_n; ++kz)
-                    for (int ky = 0; ky < k; ++ky)
-                        for (int kx = 0; kx < k; ++kx) {
-                            const int tz = dims == 3 ? phase_tap(k, pz, kz) : 0;
-                            const int ty = phase_tap(k, py, ky), tx = phase_tap(k, px, kx);
-                            acc[((size_t)co * c1 + ci) * taps1 + ((size_t)tz * k1 + ty) * k1 + tx] +=
-                                (double)w[((size_t)co * L.cin + ci) * taps + ((size_t)kz * k + ky) * k + kx];
-                        }
-        eff.resize(acc.size());
-        for (size_t i = 0; i < acc.size(); ++i) eff[i] = (float)acc[i];
+    for (int p = 0; p < (1 << dims); ++p) {
+        phase_weights(L, w, c1, p, acc);
+        eff.assign(acc.begin(), acc.end());
         pack_weights(*ph.ki_low, eff.data(), L.cout, c1, ph.n_cog_low, ph.n_chunks_low, packed);
         if (upload(ctx, m, packed.data(), packed.size(), &ph.d_w_low[p])) return 1;
     }
-    eff.resize((size_t)L.cout * c2 * taps);
-    for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < c2; ++ci)
-            memcpy(&eff[((size_t)co * c2 + ci) * taps], &w[((size_t)co * L.cin + c1 + ci) * taps], taps * sizeof(float));
+    skip_weights(L, w, c1, c2, eff);
     pack_weights(*ph.ki_skip, eff.data(), L.cout, c2, ph.n_cog_skip, ph.n_chunks_skip, packed);
     if (upload(ctx, m, packed.data(), packed.size(), &ph.d_w_skip)) return 1;
     ph.valid = true;
@@ -285,18 +297,14 @@ void pack_weights_split(const SplitKernelInfo& ki, const float* w, int cout, int
 }
 
 const SplitKernelInfo* pick_split(int k, int dil, int cout, int epi, int kx) {
-    const SplitKernelInfo* best = nullptr;
-    int best_padded = 1 << 30;
-    for (int mt : MT_CHOICES) {
-        const SplitKernelInfo* c = find_split(k, dil, mt, epi, kx);
-        if (!c) continue;
-        const int padded = (cout + mt - 1) / mt * mt;
-        if (padded < best_padded || (padded == best_padded && best && mt > best->MT)) {
-            best = c;
-            best_padded = padded;
-        }
-    }
-    return best;
+    return pick_by_padded_width(cout, [&](int mt) { return find_split(k, dil, mt, epi, kx); });
+}
+
+int upload_halfs(tpz_ctx* ctx, tpz_model* m, const std::vector<uint16_t>& h, void** out) {
+    float* d = nullptr;
+    if (upload(ctx, m, reinterpret_cast<const float*>(h.data()), (h.size() + 1) / 2, &d)) return 1;
+    *out = d;
+    return 0;
 }
 
 namespace {
@@ -335,9 +343,7 @@ int upload_split_weights(tpz_ctx* ctx, tpz_model* m, const SplitKernelInfo& ks, 
     std::vector<uint16_t> packed;
     std::vector<float> inv;
     pack_weights_split_stacked(ks, w, cout, cin, n_cog, n_chunks, packed, inv, kz_n);
-    float* d = nullptr;
-    if (upload(ctx, m, reinterpret_cast<const float*>(packed.data()), (packed.size() + 1) / 2, &d)) return 1;
-    *d_w = d;
+    if (upload_halfs(ctx, m, packed, d_w)) return 1;
     return upload_chan(ctx, m, inv.data(), inv.size(), d_ws);
 }
 
@@ -376,16 +382,7 @@ int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, LayerRT& rt
     std::vector<uint16_t> all_w, packed;
     for (int p = 0; p < (1 << dims); ++p) {
         const int px = p & 1, py = (p >> 1) & 1, pz = dims == 3 ? (p >> 2) & 1 : 0;
-        acc.assign((size_t)L.cout * c1 * taps1, 0.0);
-        for (int co = 0; co < L.cout; ++co)
-            for (int ci = 0; ci < c1; ++ci)
-                for (int kz = 0; kz < kz_n; ++kz)
-                    for (int ky = 0; ky < k; ++ky)
-                        for (int kx = 0; kx < k; ++kx) {
-                            const int tz = dims == 3 ? phase_tap(k, pz, kz) : 0;
-                            acc[((size_t)co * c1 + ci) * taps1 + ((size_t)tz * k1 + phase_tap(k, py, ky)) * k1 + phase_tap(k, px, kx)] +=
-                                (double)w[((size_t)co * L.cin + ci) * taps + ((size_t)kz * k + ky) * k + kx];
-                        }
+        phase_weights(L, w, c1, p, acc);
         eff.assign((size_t)L.cout * c1e * taps1, 0.f);
         for (int co = 0; co < L.cout; ++co)
             for (size_t i = 0; i < (size_t)c1 * taps1; ++i) eff[(size_t)co * c1e * taps1 + i] = (float)acc[(size_t)co * c1 * taps1 + i];
@@ -451,22 +448,14 @@ int prepare_split_phases(tpz_ctx* ctx, tpz_model* m, const float* w, LayerRT& rt
     }
     if (sp.ks_sub) {
         all_w.clear(); all_s.clear();
-        int nch = 0;
-        void* dw = nullptr;
-        if (upload_split_weights(ctx, m, *sp.ks_sub, sub_w.data(), 4 * L.cout, sp.sub_with_skip ? c1 + 8 : c1, &sp.n_cog_sub, &nch, &dw, &sp.d_ws_low)) return 1;
-        sp.d_w_low = dw;
-        sp.n_chunks_low = nch;
+        if (upload_split_weights(ctx, m, *sp.ks_sub, sub_w.data(), 4 * L.cout, sp.sub_with_skip ? c1 + 8 : c1, &sp.n_cog_sub,
+                                 &sp.n_chunks_low, &sp.d_w_low, &sp.d_ws_low)) return 1;
     } else {
-        float* d = nullptr;
-        if (upload(ctx, m, reinterpret_cast<const float*>(all_w.data()), (all_w.size() + 1) / 2, &d)) return 1;
-        sp.d_w_low = d;
+        if (upload_halfs(ctx, m, all_w, &sp.d_w_low)) return 1;
         if (upload(ctx, m, all_s.data(), all_s.size(), &sp.d_ws_low)) return 1;
     }
     if (sp.ks_skip) {
-        eff.resize((size_t)L.cout * c2 * taps);
-        for (int co = 0; co < L.cout; ++co)
-            for (int ci = 0; ci < c2; ++ci)
-                memcpy(&eff[((size_t)co * c2 + ci) * taps], &w[((size_t)co * L.cin + c1 + ci) * taps], taps * sizeof(float));
+        skip_weights(L, w, c1, c2, eff);
         if (upload_split_weights(ctx, m, *sp.ks_skip, eff.data(), L.cout, c2, &sp.n_cog_skip, &sp.n_chunks_skip,
                                  &sp.d_w_skip, &sp.d_ws_skip, kz_n)) return 1;
     }
@@ -661,9 +650,7 @@ int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
         std::vector<float> inv;
         pack_weights_split(*kf, blob + L.w_off, L.cout, L.cin, rt.f_n_cog, rt.f_n_chunks, packed, inv, blob + P.w_off, P.cin,
                            mul.empty() ? nullptr : mul.data());
-        float* d = nullptr;
-        if (upload(ctx, m, reinterpret_cast<const float*>(packed.data()), (packed.size() + 1) / 2, &d)) return 1;
-        rt.d_wfold = d;
+        if (upload_halfs(ctx, m, packed, &rt.d_wfold)) return 1;
         if (upload_chan(ctx, m, inv.data(), inv.size(), &rt.d_wscale_fold)) return 1;
         if (upload_chan(ctx, m, bias.data(), bias.size(), &rt.d_bias_fold)) return 1;
         rt.ks_fold = kf;
@@ -681,9 +668,7 @@ int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
         const tpz_layer& L = rt.L;
         if (L.op != TPZ_OP_CONV) continue;
         ++m->n_conv;
-        const bool on = rt.ks || rt.ks_stem || rt.ks_last || rt.sphase.valid || rt.ki_stem_split ||
-                        (rt.folded_into >= 0 && m->layers[rt.folded_into].ks_fold);
-        if (on) { ++m->n_conv_split; continue; }
+        if (split_forms(m, i)) { ++m->n_conv_split; continue; }       // any form conv_plan can choose in a 2xf16 pass
         char buf[96];
         snprintf(buf, sizeof buf, "%s#%d %dx%d d%d %d->%d", m->off_path.empty() ? "" : ", ", i, L.k, L.k, L.dil, L.cin, L.cout);
         if (m->off_path.size() < 400) m->off_path += buf;
@@ -870,24 +855,10 @@ void tpz_model_free(tpz_model* m) {
 
 int tpz_model_out_shape(tpz_model* m, int D, int H, int W, int* Do, int* Ho, int* Wo) {
     if (!m) return fail(nullptr, "model is NULL");
-    struct S { int C, D, H, W; };
-    std::vector<S> s(m->n_slots, S{0, 0, 0, 0});
-    s[0] = {1, D, H, W};
-    for (auto& rt : m->layers) {
-        const tpz_layer& L = rt.L;
-        const S& g = L.src2 >= 0 ? s[L.src2] : s[L.src];
-        if (L.op == TPZ_OP_CONV) {
-            const int span = L.dil * (L.k - 1);
-            s[L.dst] = {L.head ? 1 : L.cout, L.dims == 3 ? g.D + 2 * L.pad - span : 1, g.H + 2 * L.pad - span,
-                        g.W + 2 * L.pad - span};
-        } else if (L.op == TPZ_OP_MAXPOOL) {
-            const int span = L.dil * (L.k - 1);
-            s[L.dst] = {g.C, L.dims == 3 ? g.D - span : 1, g.H - span, g.W - span};
-        } else {
-            s[L.dst] = {g.C, L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};
-        }
-    }
-    const S& o = s[m->layers.back().L.dst];
+    std::vector<Dhw> s(m->n_slots, Dhw{0, 0, 0});
+    s[0] = {D, H, W};
+    for (auto& rt : m->layers) s[rt.L.dst] = layer_out_dhw(rt.L, s[rt.L.src2 >= 0 ? rt.L.src2 : rt.L.src]);
+    const Dhw& o = s[m->layers.back().L.dst];
     if (Do) *Do = o.D;
     if (Ho) *Ho = o.H;
     if (Wo) *Wo = o.W;
