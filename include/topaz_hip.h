@@ -42,8 +42,15 @@ typedef struct tpz_model tpz_model;
 enum {
     TPZ_OP_CONV = 1,
     TPZ_OP_MAXPOOL2 = 2,     /* MaxPool(2) with floor (the U-Net encoders, denoising/models.py:81-97) */
-    TPZ_OP_MAXPOOL = 3       /* k^dims max over a window dilated by `dil`, stride 1, no padding: the FILLED form of
-                                MaxPool(3, stride = 2) in ResNet6 and the --pooling max ResNets (resnet.py:10-47,254-339) */
+    TPZ_OP_MAXPOOL = 3,      /* k^dims max over a window dilated by `dil`, stride 1, `pad` elements of -inf padding per side
+                                (output n + 2 * pad - dil * (k - 1)): the FILLED form of a max-pool with stride 2.
+                                pad = 0: MaxPool(3, stride = 2) of ResNet6 and the --pooling max ResNets (resnet.py:10-47,254-339).
+                                pad = 1 (k = 3, pad <= dil): MaxPool(3, stride = 2, padding = 1) of a conv31/63/127 stack trained
+                                with --pooling max (basic.py:33-39,54-56,81-89) -- its score map is 2 * (dil - 1) smaller per pool */
+    TPZ_OP_AVGPOOL = 4       /* 3^dims mean, stride 1, k = 3, dil = 1, pad = 1: zero padding, divisor 3^dims everywhere
+                                (count_include_pad).  The FILLED form of AvgPool(3, stride = 2, padding = 1) of a conv31/63/127
+                                stack trained with --pooling avg: fill() sets its stride to 1 and, the module having no
+                                `dilation`, nothing else (basic.py:81-89); it preserves the size */
 };
 
 typedef struct tpz_layer {
@@ -58,7 +65,7 @@ typedef struct tpz_layer {
     int32_t cout;
     int32_t k;         /* cubic kernel size */
     int32_t dil;       /* dilation (the "filled" stride->dilation rewrite, resnet.py:87-92,153-164) */
-    int32_t pad;       /* zero padding on every side */
+    int32_t pad;       /* padding on every side: zeros (CONV, AVGPOOL), -inf (MAXPOOL) */
     float slope;       /* activation y = v > 0 ? v : slope*v : 0 = ReLU, 0.1 = LeakyReLU, 1 = none, else PReLU */
     int64_t w_off;     /* offset (floats) of the [cout][cin][k(][k)][k] weights in the blob */
     int64_t b_off;     /* offset of the [cout] bias, -1 = none */
@@ -231,6 +238,12 @@ int tpz_conv(tpz_ctx* ctx, int dims, const float* d_in, int cin1, int D1, int H1
              int pad, float slope, const float* d_res, int res_crop, const float* h_post_scale,
              const float* h_post_shift, const float* h_head_w, float head_b, float* d_out);
 int tpz_maxpool2(tpz_ctx* ctx, int dims, const float* d_in, int C, int D, int H, int W, float* d_out);
+/* one padded 3^dims pool as the layer program runs it: op = TPZ_OP_MAXPOOL (window dilated by dil, pad <= dil elements of -inf
+ * padding) or TPZ_OP_AVGPOOL (dil = 1, pad = 1).  d_in [C][D][H][W] -> d_out [C][Do][Ho][Wo], Xo = X + 2 * pad - 2 * dil.
+ * split = 0: the fp32-plane kernel; split = 1: d_in is converted to split f16 cells, pooled by the split-cell kernel and converted
+ * back (values beyond the f16 range do not survive that: *overflow = 1, may be NULL).  Synchronises. */
+int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, int H, int W, int dil, int pad, int split,
+             float* d_out, int* overflow);
 /* d_out[cols][rows] = d_in[rows][cols]; used by the truncated-DFT downsample (topaz/utils/image.py:38-61),
  * which runs as two GEMMs (tpz_conv with k = 1) around a transpose -- see topaz_amd/utils/image.py */
 int tpz_transpose_2d(tpz_ctx* ctx, const float* d_in, int rows, int cols, float* d_out);

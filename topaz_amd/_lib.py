@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, 'libtopaz_hip.so')
 TPZ_OP_CONV = 1
 TPZ_OP_MAXPOOL2 = 2
 TPZ_OP_MAXPOOL = 3
+TPZ_OP_AVGPOOL = 4
 
 
 class TpzLayer(C.Structure):
@@ -79,6 +80,8 @@ _SIGNATURES = {
                            C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, _P, _P,
                            C.c_float, _P]),
     'tpz_maxpool2': (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    'tpz_pool': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                           C.POINTER(C.c_int)]),
     'tpz_transpose_2d': (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     'tpz_ctx_set_exact': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_lanes': (C.c_int, [_P, C.c_int]),

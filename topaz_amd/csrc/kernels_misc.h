@@ -21,6 +21,10 @@ hipError_t launch_maxpool2_split(const void* in, void* out, int C, int D, int H,
 hipError_t launch_maxpoolz_split(const float* in, float* out, int C, int D, int H, int W, hipStream_t s);   // z pairs only (split cells)
 hipError_t launch_maxpoolk(const void* in, void* out, int C, int D, int H, int W, int k, int dil, int dims, bool split,
                            hipStream_t s);
+// padded 3^dims pools, stride 1 (pool_pad.hip): dilated max with -inf padding / plain mean with zero padding and divisor 3^dims;
+// out is X + 2 * pad - 2 * dil per axis; 0 <= pad <= dil
+hipError_t launch_pool_pad(const void* in, void* out, int C, int D, int H, int W, int dil, int pad, int dims, bool mean, bool split,
+                           hipStream_t s);
 hipError_t launch_shiftx_split(const float* in, void* out, int K, int pad, size_t rows, int W, int Wo, unsigned* flag,
                                hipStream_t s, size_t r0 = 0, size_t r1 = (size_t)-1, int x0 = 0, int x1 = 0x7fffffff);
 hipError_t launch_shiftsum(const float* Y, float* out, int K, size_t rows, int W, int Wp, float bias, const float* nrm,

@@ -25,8 +25,8 @@ int batch_that_fits(tpz_ctx* ctx, const tpz_model* m, int D, int H, int W) {
             const int span = L.dil * (L.k - 1);
             s[L.dst] = {L.head ? 1 : L.cout, L.dims == 3 ? g.D + 2 * L.pad - span : 1, g.H + 2 * L.pad - span, g.W + 2 * L.pad - span};
             if (L.cin == 1 || L.cout == 1) per += 32.0 * ((L.k + 7) / 8) * (double)g.D * g.H * g.W;   // column-kernel copies
-        } else if (L.op == TPZ_OP_MAXPOOL) {
-            const int span = L.dil * (L.k - 1);
+        } else if (L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) {
+            const int span = L.dil * (L.k - 1) - 2 * L.pad;
             s[L.dst] = {g.C, L.dims == 3 ? g.D - span : 1, g.H - span, g.W - span};
         } else {
             s[L.dst] = {g.C, L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};

@@ -749,7 +749,7 @@ std::vector<Rect> need_regions(const tpz_model* m, int D0, int H0, int W0, const
             if (pl.form == FORM_FOLDED_AWAY) return bail(2);
             if (split && !form_windowable(pl.form, rt, dims)) return bail(3);
             fmt[L.dst] = pl.split_dst;
-        } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL) {
+        } else if (L.op == TPZ_OP_MAXPOOL2 || (L.op == TPZ_OP_MAXPOOL && L.pad == 0)) {      // (a padded pool: bail(4), not windowed)
             fmt[L.dst] = fmt[L.src] && i != nl - 1;                // pooled in the format the source has
         } else {
             return bail(4);
@@ -925,7 +925,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             dst.pooled = false;
             slots[L.src].owned = false;
             slots[L.src].alt = nullptr;
-        } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL) {
+        } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) {
             if (s1.pitch != s1.W || s1.ps != (long long)s1.H * s1.W) { rc = fail(ctx, "maxpool needs a dense input"); break; }
             const Dhw o = layer_out_dhw(L, dhw(s1));
             if (o.D < 1 || o.H < 1 || o.W < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
@@ -941,9 +941,10 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             dst.alt = nullptr;
             dst.owned = !last;
             float* dp_ = dst.p;
-            const int k = L.k, dil = L.dil, dims = L.dims;
-            const bool by2 = L.op == TPZ_OP_MAXPOOL2;
+            const int k = L.k, dil = L.dil, dims = L.dims, pad = L.pad;
+            const bool by2 = L.op == TPZ_OP_MAXPOOL2, padded = is_padded_pool(L), mean = L.op == TPZ_OP_AVGPOOL;
             const hipError_t e = enqueue(ctx, [=](hipStream_t st) {
+                if (padded) return launch_pool_pad(src_p, dp_, Cs, Ds, Hs, Ws, dil, pad, dims, mean, sp, st);   // (pad = 0: the kernel below, as before)
                 if (!by2) return launch_maxpoolk(src_p, dp_, Cs, Ds, Hs, Ws, k, dil, dims, sp, st);
                 return sp ? launch_maxpool2_split(src_p, dp_, Cs, Ds, Hs, Ws, dims, st) : launch_maxpool2(src_p, dp_, Cs, Ds, Hs, Ws, dims, st);
             });

@@ -27,14 +27,26 @@ int model_halo(const tpz_model* m) {
     for (const LayerRT& rt : m->layers) {
         const tpz_layer& L = rt.L;
         if (L.op == TPZ_OP_CONV) h += std::max(L.pad, L.dil * (L.k - 1) - L.pad);        // (an upper bound: every layer counted)
-        else if (L.op == TPZ_OP_MAXPOOL) h += L.dil * (L.k - 1);
+        else if (L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) h += std::max(L.pad, L.dil * (L.k - 1) - L.pad);
         else return -1;                                                                   // (pooling by 2: not equivariant)
     }
     return (h + 1) & ~1;
 }
 
+// A program with a padded pool -- a conv31/63/127 stack trained with --pooling max|avg -- is not tiled: a tile's own -inf / zero
+// padding ring would have to be told from the image's, and the bit-identity argument above has not been made for it.
+bool has_padded_pool(const tpz_model* m) {
+    for (const LayerRT& rt : m->layers)
+        if (is_padded_pool(rt.L)) return true;
+    return false;
+}
+
 int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, int Do, int Ho, int Wo, bool split) {
     tpz_ctx* ctx = m->ctx;
+    if (D == 1 && (long long)H * W > ctx->tile_limit_px && has_padded_pool(m))
+        return fail(ctx, "a %d x %d image is above the tiling limit (%lld pixels, tpz_ctx_set_tiling) and this model, a conv31/63/127 "
+                         "stack trained with --pooling max|avg, has padded pools and is not scored in tiles: score it in patches", H, W,
+                    ctx->tile_limit_px);
     const int halo = (D == 1 && Ho == H && Wo == W) ? model_halo(m) : -1;
     if (halo < 0 || (long long)H * W <= ctx->tile_limit_px) {
         std::vector<Slot> slots(m->n_slots);
@@ -253,6 +265,46 @@ int tpz_maxpool2(tpz_ctx* ctx, int dims, const float* d_in, int C, int D, int H,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, launch_maxpool2(d_in, d_out, C, D, H, W, dims, ctx->stream));
     return 0;
+}
+
+int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, int H, int W, int dil, int pad, int split,
+             float* d_out, int* overflow) {
+    if (!ctx || !d_in || !d_out) return fail(ctx, "tpz_pool: NULL argument");
+    if (overflow) *overflow = 0;
+    if (op != TPZ_OP_MAXPOOL && op != TPZ_OP_AVGPOOL) return fail(ctx, "tpz_pool: op must be TPZ_OP_MAXPOOL or TPZ_OP_AVGPOOL");
+    if ((dims != 2 && dims != 3) || C < 1 || H < 1 || W < 1 || (dims == 3 && D < 1)) return fail(ctx, "tpz_pool: bad shape");
+    if (dil < 1 || pad < 0 || pad > dil) return fail(ctx, "tpz_pool: needs 0 <= pad <= dil");
+    if (op == TPZ_OP_AVGPOOL && (dil != 1 || pad != 1)) return fail(ctx, "tpz_pool: the mean takes dil = 1, pad = 1");
+    if (dims == 2) D = 1;
+    const int grow = 2 * pad - 2 * dil;
+    const int Do = dims == 3 ? D + grow : 1, Ho = H + grow, Wo = W + grow;
+    if (Do < 1 || Ho < 1 || Wo < 1) return fail(ctx, "tpz_pool: input too small");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const bool mean = op == TPZ_OP_AVGPOOL;
+    int rc = 0;
+    if (!split) {
+        HIPCHK(ctx, launch_pool_pad(d_in, d_out, C, D, H, W, dil, pad, dims, mean, false, ctx->stream));
+    } else {
+        // (cells are [c / 8][D * H * W]: a volume converts as an image of D * H rows)
+        float* x_s = (float*)pool_alloc(ctx, split_cells(C) * 8 * (size_t)D * H * W * 4);
+        float* y_s = (float*)pool_alloc(ctx, split_cells(C) * 8 * (size_t)Do * Ho * Wo * 4);
+        if (!x_s || !y_s) rc = fail(ctx, "out of device memory");
+        if (!rc) {
+            hipError_t e = hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream);
+            if (e == hipSuccess) e = launch_to_split(d_in, x_s, C, D * H, W, ctx->d_flag, ctx->stream);
+            if (e == hipSuccess) e = launch_pool_pad(x_s, y_s, C, D, H, W, dil, pad, dims, mean, true, ctx->stream);
+            if (e == hipSuccess) e = launch_from_split(y_s, d_out, C, Do * Ho, Wo, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, "tpz_pool: launch failed: %s", hipGetErrorString(e));
+        }
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");
+        if (!rc && overflow) *overflow = (int)*ctx->h_flag;
+        if (x_s) pool_release(ctx, x_s);
+        if (y_s) pool_release(ctx, y_s);
+        return rc;
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");
+    return rc;
 }
 
 int tpz_transpose_2d(tpz_ctx* ctx, const float* d_in, int rows, int cols, float* d_out) {

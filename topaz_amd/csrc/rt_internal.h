@@ -394,12 +394,15 @@ struct ConvPlan {
 };
 struct Dhw { int D = 1, H = 0, W = 0; };
 
-// output size of a layer (conv, MAXPOOL, MAXPOOL2) from its geometry source: the second source of a conv that has one, else the first
+// output size of a layer (conv, MAXPOOL, AVGPOOL, MAXPOOL2) from its geometry source: the second source of a conv that has one, else
+// the first.  (A MAXPOOL of the pooled ResNets has pad = 0; the pools of a pooled BasicConv stack have pad = 1: topaz_hip.h.)
 static inline Dhw layer_out_dhw(const tpz_layer& L, const Dhw& g) {
-    if (L.op != TPZ_OP_CONV && L.op != TPZ_OP_MAXPOOL) return {L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};
-    const int grow = (L.op == TPZ_OP_CONV ? 2 * L.pad : 0) - L.dil * (L.k - 1);
+    if (L.op == TPZ_OP_MAXPOOL2) return {L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};
+    const int grow = 2 * L.pad - L.dil * (L.k - 1);
     return {L.dims == 3 ? g.D + grow : 1, g.H + grow, g.W + grow};
 }
+// a pool with padding (pool_pad.hip): a program that holds one is neither tiled by run_image nor windowed by need_regions
+static inline bool is_padded_pool(const tpz_layer& L) { return L.op == TPZ_OP_AVGPOOL || (L.op == TPZ_OP_MAXPOOL && L.pad > 0); }
 
 // ---- cross-TU functions (defined in the file named)
 // rt_load.hip

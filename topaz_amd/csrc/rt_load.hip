@@ -166,6 +166,11 @@ int prepare_layer(tpz_ctx* ctx, tpz_model* m, const tpz_layer& L, const float* b
                   int c1 = 0, int c2 = 0) {
     rt.L = L;
     rt.c1 = c1; rt.c2 = c2;
+    if (L.op == TPZ_OP_MAXPOOL && (L.pad < 0 || L.pad > L.dil || (L.pad > 0 && L.k != 3) || L.dil < 1 || L.k < 1))
+        return fail(ctx, "maxpool: pad %d needs k = 3 and pad <= dil (k %d, dil %d)", L.pad, L.k, L.dil);
+    if (L.op == TPZ_OP_AVGPOOL && (L.k != 3 || L.dil != 1 || L.pad != 1)) return fail(ctx, "avgpool: only k = 3, dil = 1, pad = 1");
+    if (L.op != TPZ_OP_CONV && L.op != TPZ_OP_MAXPOOL2 && L.op != TPZ_OP_MAXPOOL && L.op != TPZ_OP_AVGPOOL) return fail(ctx, "unknown op %d", L.op);
+    if (L.op != TPZ_OP_CONV && L.dims != 2 && L.dims != 3) return fail(ctx, "pool: dims must be 2 or 3");
     if (L.op != TPZ_OP_CONV) return 0;
     if (L.dims != 2 && L.dims != 3) return fail(ctx, "conv: dims must be 2 or 3");
     const size_t taps = (L.dims == 3 ? (size_t)L.k * L.k * L.k : (size_t)L.k * L.k);
@@ -509,7 +514,7 @@ int prepare_split(tpz_ctx* ctx, tpz_model* m, const float* blob) {
             const tpz_layer& Lj = m->layers[j].L;
             const bool uses = Lj.src == slot || Lj.src2 == slot || Lj.res == slot;
             if (!uses) continue;
-            if (Lj.op == TPZ_OP_MAXPOOL2 || Lj.op == TPZ_OP_MAXPOOL) any |= slot_read_split(Lj.dst);   // pools keep the format
+            if (Lj.op == TPZ_OP_MAXPOOL2 || Lj.op == TPZ_OP_MAXPOOL || Lj.op == TPZ_OP_AVGPOOL) any |= slot_read_split(Lj.dst);   // pools keep the format
             else if (Lj.src2 == slot && m->layers[j].sphase.valid && m->layers[j].sphase.ki_skip_stem) continue;  // fp32
             else any |= reads[j] != 0;
         }

@@ -28,10 +28,16 @@ class Features:
 
 
 class LinearClassifier:
-    def __init__(self, arch: str, state_dict, dims: Optional[int] = None, pooling: bool = False, dropout: bool = False):
+    def __init__(self, arch: str, state_dict, dims: Optional[int] = None, pooling=False, dropout: bool = False):
         self.arch = arch
         self.dropout = bool(dropout)                 # trained with --dropout > 0 (matters to BasicConv.fill only, see pack.py)
-        self.pooling = bool(pooling) or arch == 'resnet6'       # MaxPool(3, stride 2) layers (resnet.py:10-47)
+        # pooling layers: False / None, True or 'max' (MaxPool(3, stride 2): resnet.py:10-47, basic.py:33-36), 'avg' (conv31/63/127
+        # only, basic.py:37-39; upstream crashes on a ResNet with --pooling avg)
+        if pooling not in (False, None, True, 'max', 'avg'):
+            raise ValueError(f'pooling = {pooling!r}: expected None, "max" or "avg"')
+        if pooling == 'avg' and arch not in pack.BASIC_SIZES:
+            raise ValueError(f'{arch} with avg pooling: only conv31 / conv63 / conv127 have it')
+        self.pooling = 'max' if (pooling is True or arch == 'resnet6') else (pooling or False)
         self.state_dict_np = OrderedDict((k, (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)))
                                          for k, v in state_dict.items())
         # 2-D or 3-D (classifier.py:17-29 `dims`): read off the 1x1(x1) head unless given
@@ -42,16 +48,19 @@ class LinearClassifier:
             raise ValueError(f'LinearClassifier: dims = {dims} with {wdims}-D weights')
         self.dims = dims
         if arch in ('resnet6', 'resnet8', 'resnet16'):
-            self._program, width = pack.pack_resnet(arch, self.state_dict_np, dims, self.pooling)
+            self._program, width = pack.pack_resnet(arch, self.state_dict_np, dims, bool(self.pooling))
             units = self.state_dict_np['features.features.0.conv.weight'].shape[0]
             bn = any(k.endswith('running_mean') for k in self.state_dict_np)
         elif arch in pack.BASIC_SIZES:
-            self._program, width = pack.pack_basicconv(pack.BASIC_SIZES[arch], self.state_dict_np, self.dropout, dims)
+            self._program, width = pack.pack_basicconv(pack.BASIC_SIZES[arch], self.state_dict_np, self.dropout, dims,
+                                                       self.pooling or None)
             units = self.state_dict_np['features.features.0.weight'].shape[0]
             bn = any(k.endswith('running_mean') for k in self.state_dict_np)
         else:
             raise ValueError(f'unsupported feature extractor {arch!r}')
         self.features = Features(arch, units, bn, width, dims)
+        if arch in pack.BASIC_SIZES:                 # (unit_scaling > 1: the last conv is wider than the first, basic.py:60,77)
+            self.features.latent_dim = int(self.state_dict_np['classifier.weight'].shape[1])
         self.filled = False
         self._device_model: Optional[DeviceModel] = None
         self._device: Optional[int] = None
@@ -80,8 +89,9 @@ class LinearClassifier:
         """LinearClassifier.fill -> ResNet.fill / BasicConv.fill: returns the total stride"""
         self.filled = True
         if self.arch.startswith('resnet'):
-            return stride * pack.resnet_fill(pack.resnet_modules(self.arch, self.pooling))
-        return stride * 2 ** (len(pack.BASIC_SIZES[self.arch]) - 1)
+            return stride * pack.resnet_fill(pack.resnet_modules(self.arch, bool(self.pooling)))
+        bn = self.features.bn
+        return stride * pack.basic_fill(len(pack.BASIC_SIZES[self.arch]), bn, self.dropout, self.pooling or None)[2]
 
     def unfill(self):
         self.filled = False

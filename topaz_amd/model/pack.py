@@ -13,7 +13,7 @@ convolution, so the 4u-channel feature map never reaches HBM.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -134,49 +134,78 @@ def pack_resnet(arch: str, sd, dims: int = 2, pooling: bool = False) -> Tuple[La
 BASIC_SIZES = {'conv127': (7, 5, 5, 5, 5), 'conv63': (7, 5, 5, 5), 'conv31': (7, 5, 5)}
 
 
-def basic_width(sizes: Sequence[int]) -> int:
-    strides = [2] * (len(sizes) - 1) + [1]
+def basic_width(sizes: Sequence[int], pooling: Optional[str] = None) -> int:
+    """insize_from_outsize(layers, 1) (model/utils.py:39-68).  Unpooled: every conv but the last has stride 2.  Pooled
+    (basic.py:33-39,54-56): stride-1 convs, pooling(3, stride=2, padding=1) after every block but the last -- a pool maps
+    n to 2 * n - 1, a strided conv n to 2 * n + k - 2: the widths come out the same, 31 / 63 / 127."""
     out = 1
-    for k, s in zip(reversed(sizes), reversed(strides)):
-        out = (out - 1) * s + 1 + (k - 1)
+    for i, k in enumerate(reversed(sizes)):
+        if i > 0:
+            out = (out - 1) * 2 + 1 + ((3 - 1) - 2 * 1 if pooling else 0)      # the pool / the conv's own stride
+        out += k - 1
     return out
 
 
-def basic_fill_dilations(n_convs: int, has_bn: bool, dropout: bool = False) -> List[int]:
-    """dilation BasicConv.fill() gives each conv (basic.py:81-89).  fill() walks the layer list zipped with `strides`,
-    and the constructor appends no `strides` entry for its nn.Dropout layers (basic.py:57-58,69-70): without dropout the
-    result is the cumulative stride 1, 2, 4, ...; a model trained with --dropout has the pairs slip by one per Dropout
-    (conv31: 1, 4, 4) and that is what upstream's `extract` then scores with -- reproduced here, not corrected."""
+def basic_fill(n_convs: int, has_bn: bool, dropout: bool = False, pooling: Optional[str] = None):
+    """What BasicConv.fill() does to the stack (basic.py:81-89): (dilation of each conv, dilation of each pool, the stride it
+    returns).  fill() walks the layer list zipped with `strides`; the constructor appends an entry for every conv, BatchNorm,
+    activation and pool and none for its nn.Dropout layers (basic.py:57-58,69-70).  A module met in the zip gets stride 1 and,
+    if it has a `dilation` attribute -- the convs and MaxPool, not AvgPool --, the stride accumulated so far as its dilation.
+    Without dropout that is the cumulative stride 1, 2, 4, ...; a model trained with --dropout has the pairs slip by one per
+    Dropout (conv31: 1, 4, 4) and that is what upstream's `extract` then scores with -- reproduced here, not corrected.
+    pooling 'max' / 'avg' (`topaz train --pooling`): the convs have stride 1 and the pools carry the 2s.  An avg pool keeps
+    dilation 1 whatever the accumulated stride; padding stays 1 on both kinds."""
     kinds, strides = [], []
     for i in range(n_convs):
         last = i == n_convs - 1
         kinds.append('conv')
-        strides.append(1 if last else 2)
+        strides.append(1 if (last or pooling) else 2)
         if has_bn:
             kinds.append('bn')
             strides.append(1)
         kinds.append('act')
         strides.append(1)
+        if pooling and not last:
+            kinds.append('pool')
+            strides.append(2)
         if dropout:
             kinds.append('drop')
-    dils, stride = [], 1
+    n_pools = kinds.count('pool')
+    dils, pool_dils, stride = [], [], 1
     for kind, st in zip(kinds, strides):
         if kind == 'conv':
             dils.append(stride)
+        elif kind == 'pool':
+            pool_dils.append(stride if pooling == 'max' else 1)
         stride *= st
-    return dils + [1] * (n_convs - len(dils))        # convs past the end of the zip keep dilation 1 (and their stride 1)
+    if len(pool_dils) < n_pools:
+        # (conv127 without BatchNorm, with dropout: the last pool lies past the end of the zip and would keep its stride 2)
+        raise NotImplementedError('this BasicConv stack (pooling and dropout, no BatchNorm) leaves a pool strided after '
+                                  "upstream's fill(): its filled forward is not a dense score map and is not supported")
+    # convs past the end of the zip keep dilation 1 (and their stride 1)
+    return dils + [1] * (n_convs - len(dils)), pool_dils, stride
 
 
-def pack_basicconv(sizes: Sequence[int], sd, dropout: bool = False, dims: int = 2) -> Tuple[LayerProgram, int]:
+def basic_fill_dilations(n_convs: int, has_bn: bool, dropout: bool = False, pooling: Optional[str] = None) -> List[int]:
+    """dilation BasicConv.fill() gives each conv: basic_fill()[0]"""
+    return basic_fill(n_convs, has_bn, dropout, pooling)[0]
+
+
+def pack_basicconv(sizes: Sequence[int], sd, dropout: bool = False, dims: int = 2,
+                   pooling: Optional[str] = None) -> Tuple[LayerProgram, int]:
     """filled basic.BasicConv (basic.py:81-89: dilation = cumulative stride 1,2,4,..) + 1x1 head.  `sd` is numbered
     without Dropout modules (unpickle.py renumbers); `dropout` only selects upstream's fill pattern for such models.
-    dims = 3: the same stack over Conv3d / BatchNorm3d weights (basic.py:23-27)."""
+    dims = 3: the same stack over Conv3d / BatchNorm3d weights (basic.py:23-27).
+    pooling 'max' / 'avg': a padded stride-1 pool behind every block but the last (basic_fill; TPZ_OP_MAXPOOL with pad 1 at the
+    accumulated dilation, TPZ_OP_AVGPOOL).  Parameter-free, but each owns an index of features.features, as the ResNet pools do."""
     sd = _np(sd)
+    if pooling not in (None, 'max', 'avg'):
+        raise ValueError(f'BasicConv stack: pooling = {pooling!r}')
     if sd['features.features.0.weight'].ndim != dims + 2:
         raise ValueError(f'BasicConv stack: the weights are {sd["features.features.0.weight"].ndim - 2}-D, dims = {dims} was asked for')
     has_bn = any(k.endswith('running_mean') for k in sd)
-    width = basic_width(sizes)
-    dils = basic_fill_dilations(len(sizes), has_bn, dropout)
+    width = basic_width(sizes, pooling)
+    dils, pool_dils, _ = basic_fill(len(sizes), has_bn, dropout, pooling)
     P = LayerProgram(dims)
     pre = 'features.features.'
     head_w = sd['classifier.weight'].reshape(-1)
@@ -193,6 +222,9 @@ def pack_basicconv(sizes: Sequence[int], sd, dropout: bool = False, dims: int = 
         last = li == len(sizes) - 1
         kw = dict(head_w=head_w, head_b=head_b) if last else {}
         cur = P.conv(cur, w, b, dil=dils[li], pad=width // 2 if li == 0 else 0, slope=slope, **kw)
+        if pooling and not last:
+            cur = P.maxpool(cur, 3, pool_dils[li], pad=1) if pooling == 'max' else P.avgpool(cur)
+            idx += 1
     return P, width
 
 

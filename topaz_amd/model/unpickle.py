@@ -131,10 +131,30 @@ def _without_dropout(sd, kinds):
     return out
 
 
+_BASIC_POOLS = {'MaxPool2d': 'max', 'MaxPool3d': 'max', 'AvgPool2d': 'avg', 'AvgPool3d': 'avg'}
+
+
+def _first(v):
+    return v[0] if isinstance(v, (tuple, list)) else v
+
+
+def _check_basic_pool(path, mod):
+    """a pool of a BasicConv stack must be the one its constructor writes: pooling(3, stride=2, padding=1), torch defaults
+    otherwise (basic.py:54-56) -- the packer reproduces fill() for that module and no other"""
+    d = mod.__dict__
+    kind = type(mod).__name__
+    want = dict(kernel_size=3, stride=2, padding=1, ceil_mode=False)
+    want.update(dict(dilation=1) if _BASIC_POOLS[kind] == 'max' else dict(count_include_pad=True, divisor_override=None))
+    for k, v in want.items():
+        if _first(d.get(k, v)) != v:
+            raise NotImplementedError(f'{path}: {kind} with {k} = {d.get(k)!r} is not the pooling(3, stride=2, padding=1) of a '
+                                      f'conv31/63/127 stack and is not supported on the MI355X path')
+
+
 def load_module_pickle(path, with_traits: bool = False):
-    """(arch, state_dict) of a pickled LinearClassifier; with_traits=True adds {'pooling': the feature stack holds MaxPool
-    layers (`topaz train --pooling max`, ResNet6), 'dropout': it was trained with --dropout > 0}.  The state_dict is
-    numbered without the Dropout modules."""
+    """(arch, state_dict) of a pickled LinearClassifier; with_traits=True adds {'pooling': 'max' / 'avg' when the feature stack
+    holds pooling layers (`topaz train --pooling max|avg`, ResNet6), else False; 'dropout': it was trained with --dropout > 0}.
+    The state_dict is numbered without the Dropout modules; a pool keeps its index."""
     obj = torch.load(path, map_location='cpu', weights_only=False, pickle_module=_PickleModule)
     if isinstance(obj, (dict, OrderedDict)) and all(torch.is_tensor(v) for v in obj.values()):
         raise ValueError(f'{path} holds a bare state_dict; the architecture cannot be inferred. '
@@ -149,16 +169,23 @@ def load_module_pickle(path, with_traits: bool = False):
     _walk(obj, '', sd)
     mods = feats.__dict__['_modules']['features'].__dict__['_modules']
     kinds = [type(m).__name__ for m in mods.values()]
-    pooling = 'MaxPool' in kinds
+    pooling = 'max' if 'MaxPool' in kinds else False
     dropout = 'Dropout' in kinds
     if fname in ('ResNet6', 'ResNet8', 'ResNet16'):
         arch = fname.lower()
         if any(k not in ('BasicConv', 'ResidA', 'MaxPool', 'Dropout') for k in kinds):
             raise NotImplementedError(f'{path}: {arch} with layers {sorted(set(kinds))} is not supported on the MI355X path')
     elif fname in ('BasicConv', 'Conv127', 'Conv63', 'Conv31'):
-        if any(not (k.startswith(('Conv', 'BatchNorm')) or k in ('PReLU', 'Dropout')) for k in kinds):
+        if any(not (k.startswith(('Conv', 'BatchNorm')) or k in ('PReLU', 'Dropout') or k in _BASIC_POOLS) for k in kinds):
             raise NotImplementedError(f'{path}: BasicConv with layers {sorted(set(kinds))} is not supported on the MI355X '
-                                      f'path (strided PReLU stacks only: no pooling, no other activation)')
+                                      f'path (PReLU stacks, strided or with max / avg pooling: no other activation or layer)')
+        pools = {_BASIC_POOLS[k] for k in kinds if k in _BASIC_POOLS}
+        if len(pools) > 1:
+            raise NotImplementedError(f'{path}: BasicConv with both max and avg pooling is not something `topaz train` writes')
+        for m in mods.values():
+            if type(m).__name__ in _BASIC_POOLS:
+                _check_basic_pool(path, m)
+        pooling = pools.pop() if pools else False
         n_convs = sum(1 for k in kinds if k.startswith('Conv'))
         arch = {5: 'conv127', 4: 'conv63', 3: 'conv31'}.get(n_convs)
         if arch is None:

@@ -341,18 +341,41 @@ class LayerProgram:
         self.layers.append(L)
         return L.dst
 
-    def maxpool(self, src: int, k: int = 3, dil: int = 1) -> int:
-        """k^dims max over a window dilated by `dil`, stride 1, no padding (TPZ_OP_MAXPOOL: a filled MaxPool(k, stride))"""
+    def maxpool(self, src: int, k: int = 3, dil: int = 1, pad: int = 0) -> int:
+        """k^dims max over a window dilated by `dil`, stride 1, `pad` elements of -inf padding (TPZ_OP_MAXPOOL: a filled
+        MaxPool(k, stride); pad = 1 needs k = 3 and is the pool of a conv31/63/127 stack trained with --pooling max)"""
+        return self._pool(_lib.TPZ_OP_MAXPOOL, src, k, dil, pad)
+
+    def avgpool(self, src: int) -> int:
+        """3^dims mean, stride 1, one element of zero padding, divisor 3^dims (TPZ_OP_AVGPOOL: the filled AvgPool(3, stride 2,
+        padding 1) of a conv31/63/127 stack trained with --pooling avg)"""
+        return self._pool(_lib.TPZ_OP_AVGPOOL, src, 3, 1, 1)
+
+    def _pool(self, op: int, src: int, k: int, dil: int, pad: int) -> int:
         L = TpzLayer()
-        L.op = _lib.TPZ_OP_MAXPOOL
+        L.op = op
         L.dims = self.dims
         L.src, L.src2, L.res = src, -1, -1
         L.dst = self.new_slot()
-        L.k, L.dil, L.pad = k, dil, 0
+        L.k, L.dil, L.pad = k, dil, pad
         L.w_off = L.b_off = L.post_scale_off = L.post_shift_off = L.head_w_off = L.head_b_off = -1
         L.slope = 1.0
         self.layers.append(L)
         return L.dst
+
+    def out_shape(self, D: int, H: int, W: int) -> Tuple[int, int, int]:
+        """size of the program's output for a D x H x W input (D = 1 in 2-D), as tpz_model_out_shape computes it on the device
+        side: a conv or pool with window k, dilation dil and padding pad maps n to n + 2 * pad - dil * (k - 1), MAXPOOL2 to n // 2"""
+        shapes = {0: (D, H, W)}
+        for L in self.layers:
+            d, h, w = shapes[L.src2 if L.op == _lib.TPZ_OP_CONV and L.src2 >= 0 else L.src]
+            if L.op == _lib.TPZ_OP_MAXPOOL2:
+                o = (d // 2 if L.dims == 3 else 1, h // 2, w // 2)
+            else:
+                grow = 2 * L.pad - L.dil * (L.k - 1)
+                o = (d + grow if L.dims == 3 else 1, h + grow, w + grow)
+            shapes[L.dst] = o
+        return shapes[self.layers[-1].dst]
 
     def flat_blob(self) -> np.ndarray:
         if not self.blob:
@@ -564,6 +587,30 @@ def maxpool2(x: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     check(ctx.lib.tpz_maxpool2(ctx.handle, dims, _ptr(x), Cc, D, H, W, _ptr(y)), ctx.handle)
     return y
+
+
+def pool(x: torch.Tensor, op: str = 'max', dil: int = 1, pad: int = 1, split: bool = False,
+         ctx: Optional[Context] = None) -> Tuple[torch.Tensor, bool]:
+    """One padded 3^dims pool through tpz_pool.  x: [C,(D,)H,W]; op 'max' (window dilated by dil, -inf padding) or 'avg' (dil = 1,
+    pad = 1, zero padding, divisor 3^dims).  split: on split f16 cells (converted on the device either side) instead of fp32 planes.
+    Returns ([C,(Do,)Ho,Wo], overflow) -- overflow: split cells could not hold an input value (beyond the f16 range, inf or NaN)."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    dims = x.dim() - 1
+    Cc = x.shape[0]
+    D = x.shape[1] if dims == 3 else 1
+    H, W = x.shape[-2], x.shape[-1]
+    grow = 2 * pad - 2 * dil
+    shape = (Cc, D + grow, H + grow, W + grow) if dims == 3 else (Cc, H + grow, W + grow)
+    if min(shape) < 1:
+        raise ValueError(f'input {tuple(x.shape)} is too small for a 3-tap pool at dilation {dil}, padding {pad}')
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    ovf = C.c_int(0)
+    code = {'max': _lib.TPZ_OP_MAXPOOL, 'avg': _lib.TPZ_OP_AVGPOOL}[op]
+    check(ctx.lib.tpz_pool(ctx.handle, code, dims, _ptr(x), Cc, D, H, W, int(dil), int(pad), 1 if split else 0, _ptr(y),
+                           C.byref(ovf)), ctx.handle)
+    return y, bool(ovf.value)
 
 
 def mean_std(x: torch.Tensor, unbiased: bool, ctx: Optional[Context] = None) -> Tuple[float, float]:
