@@ -145,6 +145,15 @@ void pool_release(tpz_ctx* ctx, void* p) {
         if (b.p == p) { b.used = false; return; }
 }
 
+// ---- the overflow flag of a 2xf16 pass: cleared on the ctx stream before the pass, read back once the stream has drained
+hipError_t flag_clear(tpz_ctx* ctx) { return hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream); }
+hipError_t flag_read(tpz_ctx* ctx, unsigned* flag, bool check_copy) {
+    const hipError_t copied = hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t drained = hipStreamSynchronize(ctx->stream);
+    *flag = *ctx->h_flag;
+    return check_copy && copied != hipSuccess ? copied : drained;
+}
+
 float* next_nrm(tpz_ctx* ctx) {
     if (ctx->nrm_next >= NRM_RING) {
         if (ctx->lanes_on) (void)hipDeviceSynchronize();     // the other lane may still read blocks of this ring

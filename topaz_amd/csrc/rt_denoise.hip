@@ -14,26 +14,19 @@ namespace {
 // below 2 the pass falls back to single patches on the lanes.
 int batch_that_fits(tpz_ctx* ctx, const tpz_model* m, int D, int H, int W) {
     if (ctx->batch < 2) return ctx->batch;
-    struct S { int C, D, H, W; };
-    std::vector<S> s(m->n_slots, S{0, 0, 0, 0});
-    s[0] = {1, D, H, W};
+    struct S { int C; Dhw g; };
+    std::vector<S> s(m->n_slots, S{0, {0, 0, 0}});
+    s[0] = {1, {D, H, W}};
     double per = 3.0 * 4.0 * D * H * W;                          // the tile, its normalised copy, the result
     for (auto& rt : m->layers) {
         const tpz_layer& L = rt.L;
-        const S& g = L.src2 >= 0 ? s[L.src2] : s[L.src];
-        if (L.op == TPZ_OP_CONV) {
-            const int span = L.dil * (L.k - 1);
-            s[L.dst] = {L.head ? 1 : L.cout, L.dims == 3 ? g.D + 2 * L.pad - span : 1, g.H + 2 * L.pad - span, g.W + 2 * L.pad - span};
-            if (L.cin == 1 || L.cout == 1) per += 32.0 * ((L.k + 7) / 8) * (double)g.D * g.H * g.W;   // column-kernel copies
-        } else if (L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) {
-            const int span = L.dil * (L.k - 1) - 2 * L.pad;
-            s[L.dst] = {g.C, L.dims == 3 ? g.D - span : 1, g.H - span, g.W - span};
-        } else {
-            s[L.dst] = {g.C, L.dims == 3 ? g.D / 2 : 1, g.H / 2, g.W / 2};
-        }
-        const S& o = s[L.dst];
+        const S src = L.src2 >= 0 ? s[L.src2] : s[L.src];
+        const Dhw g = src.g, o = layer_out_dhw(L, g);
+        const int C = L.op != TPZ_OP_CONV ? src.C : L.head ? 1 : L.cout;
+        s[L.dst] = {C, o};
+        if (L.op == TPZ_OP_CONV && (L.cin == 1 || L.cout == 1)) per += 32.0 * ((L.k + 7) / 8) * (double)g.D * g.H * g.W;   // column-kernel copies
         if (o.D < 1 || o.H < 1 || o.W < 1) return ctx->batch;     // (the pass itself reports the bad geometry)
-        per += 32.0 * split_cells(o.C) * (double)o.D * o.H * o.W;
+        per += 32.0 * split_cells(C) * (double)o.D * o.H * o.W;
     }
     double avail = (double)ctx->batch_mem;
     if (ctx->batch_mem <= 0) {
@@ -243,11 +236,11 @@ int tpz_denoise_2d(tpz_model* m, const float* d_in, int H, int W, int patch, int
     if (Ho != 8 * 64 || Wo != 8 * 64) return fail(ctx, "tpz_denoise_2d: the model does not preserve the image size");
     if (m->split_ok && !ctx->exact) {
         // 2xf16 path for the whole micrograph; any activation beyond the f16 range re-runs it on the fp32 kernels
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream));
+        unsigned overflow = 0;
+        HIPCHK(ctx, flag_clear(ctx));
         if (denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, true)) return 1;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (*ctx->h_flag == 0) { ++m->n_split; return 0; }
+        HIPCHK(ctx, flag_read(ctx, &overflow));
+        if (overflow == 0) { ++m->n_split; return 0; }
         ++m->n_fallback;
     }
     return denoise_2d_pass(m, d_in, H, W, patch, pad, d_out, false);
@@ -262,11 +255,11 @@ int tpz_denoise_3d_shard(tpz_model* m, const float* d_in, int D, int H, int W, i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (m->split_ok && !ctx->exact) {
         // 2xf16 path for the whole tomogram; any activation beyond the f16 range re-runs it on the fp32 kernels
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream));
+        unsigned overflow = 0;
+        HIPCHK(ctx, flag_clear(ctx));
         if (denoise_3d_pass(m, d_in, D, H, W, patch, pad, d_out, true, shard, n_shards)) return 1;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (*ctx->h_flag == 0) { ++m->n_split; return 0; }
+        HIPCHK(ctx, flag_read(ctx, &overflow));
+        if (overflow == 0) { ++m->n_split; return 0; }
         ++m->n_fallback;
     }
     return denoise_3d_pass(m, d_in, D, H, W, patch, pad, d_out, false, shard, n_shards);

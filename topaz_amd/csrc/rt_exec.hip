@@ -7,16 +7,57 @@
 namespace tpz::rt {
 namespace {
 
-// grid, XCD swizzle and phase stagger of one conv_mfma launch; a.Dout/Hout/Wout, n_chunks, cog_inner are set
-int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int n_cog, double flops) {
+Dhw dhw(const Slot& s) { return {s.D, s.H, s.W}; }
+
+// ---- the launch window: one rule for what a launch computes of its lattice, what that costs and the tiles that cover it
+// planes [z0, z1), rows [y0, y1) and columns [x0, x1) of the lattice a launch computes (2-D: the one plane [0, 1))
+struct Window { int z0, z1, y0, y1, x0, x1; };
+
+// The window of a launch over the lattice `lat` from the part `need` of the layer's tensor that anything reads (need_regions; off:
+// the whole lattice).  `scale` = 2: `lat` is the half-resolution lattice of a per-parity / sub-pixel launch; `align_x`: the left
+// edge is rounded down to a multiple of it.  At least one plane, row and column: need_regions only hands out non-empty boxes
+// inside the tensor (the kept pixels are one, and every step of its backward walk clips a grown, non-empty box to the tensor it
+// lies in), so the guard changes no window it asks for.
+Window launch_window(const Rect& need, const Dhw& lat, int scale = 1, int align_x = 1) {
+    Window w = {0, std::max(lat.D, 1), 0, lat.H, 0, lat.W};
+    if (!need.on) return w;
+    w.y0 = need.y0 / scale; w.x0 = (need.x0 / scale) & ~(align_x - 1);
+    w.y1 = std::max(w.y0 + 1, std::min(lat.H, (need.y1 + scale - 1) / scale));
+    w.x1 = std::max(w.x0 + 1, std::min(lat.W, (need.x1 + scale - 1) / scale));
+    if (lat.D > 1) {          // 3-D: the planes of the box
+        w.z0 = std::min(lat.D - 1, need.z0 / scale);
+        w.z1 = std::max(w.z0 + 1, std::min(lat.D, (need.z1 + scale - 1) / scale));
+    }
+    return w;
+}
+// (the two descriptors encode z differently: the fp32 kernels take the planes [wz0, wz1) of a.Dout, the plane-stacked 2xf16 kernels
+// the first plane and, as a.Dout, the number of planes of a.Dlat)
+void apply_window(ConvArgs& a, const Window& w) {
+    a.wz0 = w.z0; a.wz1 = w.z1; a.wy0 = w.y0; a.wy1 = w.y1; a.wx0 = w.x0; a.wx1 = w.x1;
+}
+void apply_window(SplitArgs& a, const Window& w) {
+    a.wy0 = w.y0; a.wy1 = w.y1; a.wx0 = w.x0; a.wx1 = w.x1;
+    if (a.Dout > 1) { a.wz0 = w.z0; a.Dout = w.z1 - w.z0; }
+}
+// the share of the lattice that lies in the window: the FLOP a windowed launch executes of its layer's
+double window_share(const Window& w, const Dhw& lat) {
+    return (double)(w.y1 - w.y0) * (w.x1 - w.x0) / ((double)lat.H * lat.W) * ((double)(w.z1 - w.z0) / std::max(lat.D, 1));
+}
+// algorithmic FLOP of a conv layer over the output lattice `o`
+double conv_flops(int cout, int cin, int k, int dims, const Dhw& o) {
+    return 2.0 * cout * cin * std::pow((double)k, dims) * (double)o.D * o.H * o.W;
+}
+// tiles of `t` outputs that cover `n`, in whole groups of `d` (the tiles of a kernel of dilation d interleave: d of them share rows)
+int tile_count(int n, int t, int d = 1) { return (n + t * d - 1) / (t * d) * d; }
+
+// window, grid, XCD swizzle and phase stagger of one conv_mfma launch; a.Dout/Hout/Wout (the lattice), n_chunks, cog_inner are set
+int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int n_cog, double flops, const Window& w) {
     a.xcd_swizzle = 1;
-    if (a.wy1 <= 0) { a.wy0 = a.wx0 = 0; a.wy1 = a.Hout; a.wx1 = a.Wout; }      // no window: the whole lattice
-    else flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
-    if (a.wz1 <= 0 || ki.dims != 3) { a.wz0 = 0; a.wz1 = std::max(a.Dout, 1); }  // no z window (every 2-D launch): the whole depth
-    else flops *= (double)(a.wz1 - a.wz0) / a.Dout;
-    a.tiles_x = (a.wx1 - a.wx0 + ki.TW - 1) / ki.TW;
-    a.tiles_y = (a.wy1 - a.wy0 + ki.TH * ki.D - 1) / (ki.TH * ki.D) * ki.D;
-    a.tiles_z = ki.dims == 3 ? (a.wz1 - a.wz0 + ki.TD * ki.D - 1) / (ki.TD * ki.D) * ki.D : 1;
+    apply_window(a, w);
+    flops *= window_share(w, {a.Dout, a.Hout, a.Wout});
+    a.tiles_x = tile_count(w.x1 - w.x0, ki.TW);
+    a.tiles_y = tile_count(w.y1 - w.y0, ki.TH, ki.D);
+    a.tiles_z = ki.dims == 3 ? tile_count(w.z1 - w.z0, ki.TD, ki.D) : 1;
     a.stagger_first = a.stagger_sleeps = 0;
     // phase stagger of the two workgroups per CU (conv_mfma.h); only worth it for many generations
     if ((long long)a.tiles_x * a.tiles_y >= 4096) {
@@ -36,25 +77,14 @@ int launch_mfma(tpz_ctx* ctx, const ConvKernelInfo& ki, ConvArgs& a, int n_cog, 
     return 0;
 }
 
-// launch window of an fp32 kernel from the part of the layer's tensor that is needed (`scale` = 2: the half-resolution lattice of
-// a per-parity launch).  The left edge is rounded down to a multiple of 4 pixels: the 16-byte granules of the MFMA kernels'
-// loader stay aligned; the few extra columns are computed like any others.
-void set_window(ConvArgs& a, const Rect& need, int scale = 1) {
-    if (!need.on) return;
-    a.wy0 = need.y0 / scale; a.wx0 = (need.x0 / scale) & ~3;
-    a.wy1 = std::min(a.Hout, (need.y1 + scale - 1) / scale);
-    a.wx1 = std::min(a.Wout, (need.x1 + scale - 1) / scale);
-    a.wy1 = std::max(a.wy1, a.wy0 + 1); a.wx1 = std::max(a.wx1, a.wx0 + 1);
-    if (a.Dout > 1) {          // 3-D: the planes of the box
-        a.wz0 = std::min(a.Dout - 1, need.z0 / scale);
-        a.wz1 = std::max(a.wz0 + 1, std::min(a.Dout, (need.z1 + scale - 1) / scale));
-    }
-}
+// The windows of the fp32 kernels start on a multiple of 4 pixels: the 16-byte granules of the MFMA kernels' loader stay aligned;
+// the few extra columns are computed like any others.
+enum { FP32_ALIGN_X = 4 };
 
 // conv(cat(upsample2x(s1), s2)) by output parity (prepare_phases): 2^dims plain launches over s1 that write the
-// strided output positions, then the skip-source launch over the full grid that adds itself in place.
-int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const Slot& s1, const Slot& s2,
-                    Slot& dst) {
+// strided output positions, then the skip-source launch over the full grid (its window: `full`) that adds itself in place.
+int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const Slot& s1, const Slot& s2, Slot& dst,
+                    const Window& full) {
     const tpz_layer& L = rt.L;
     const LayerRT::Phase& ph = rt.phase;
     const int n_phase = 1 << L.dims;
@@ -76,10 +106,9 @@ int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const
         a.os = 2; a.oox = px; a.ooy = py; a.ooz = pz;
         a.n_chunks = ph.n_chunks_low;
         a.cog_inner = 1;
-        a.wy0 = a.wx0 = a.wy1 = a.wx1 = a.wz0 = a.wz1 = 0;
-        set_window(a, dst.need, 2);
-        const double fl = 2.0 * L.cout * ph.c1 * std::pow((double)ph.k1, L.dims) * (double)s1.D * s1.H * s1.W;
-        if (launch_mfma(ctx, *ph.ki_low, a, ph.n_cog_low, fl)) return 1;
+        if (launch_mfma(ctx, *ph.ki_low, a, ph.n_cog_low, conv_flops(L.cout, ph.c1, ph.k1, L.dims, dhw(s1)),
+                        launch_window(dst.need, dhw(s1), 2, FP32_ALIGN_X)))
+            return 1;
     }
     ConvArgs a = base;
     a.in = s2.p;
@@ -92,15 +121,15 @@ int run_conv_phases(tpz_ctx* ctx, const LayerRT& rt, const ConvArgs& base, const
     a.cs1 = s2.cs; a.ps1 = s2.ps; a.pitch1 = s2.pitch;
     a.n_chunks = ph.n_chunks_skip;
     a.cog_inner = 1;
-    const double fl = 2.0 * L.cout * ph.c2 * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
-    return launch_mfma(ctx, *ph.ki_skip, a, ph.n_cog_skip, fl);
+    return launch_mfma(ctx, *ph.ki_skip, a, ph.n_cog_skip, conv_flops(L.cout, ph.c2, L.k, L.dims, dhw(dst)), full);
 }
 
-int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops);
+int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops, const Window& w);
 
 // What every 2xf16 launch shares.  `in`: cells1 cells of g_in; the launch computes the lattice `lat` (kz taps along z, kz = 0: a 2-D
 // launch; `pad` on every axis), element o of which is element o * os (+ the parity) of the full output tensor `full`.  The window is
-// the whole lattice, Dlat its depth.  The caller adds its operands, a second source and whatever else is particular to it.
+// the whole lattice, Dlat its depth, until the launcher applies the launch's own.  The caller adds its operands, a second source and
+// whatever else is particular to it.
 SplitArgs split_args(tpz_ctx* ctx, const void* in, int cells1, const Dhw& g_in, int cout, const Dhw& lat, int os, const Dhw& full,
                      int kz, int pad, float slope) {
     SplitArgs a;
@@ -119,41 +148,20 @@ SplitArgs split_args(tpz_ctx* ctx, const void* in, int cells1, const Dhw& g_in, 
     if (kz > 0) { a.KZ = kz; a.pad_z = pad; a.Din = g_in.D; a.Dout = a.Dlat = lat.D; a.Dfull = full.D; a.Dres = 1; }
     return a;
 }
-Dhw dhw(const Slot& s) { return {s.D, s.H, s.W}; }
-
-// narrows the window of a launch to the part of the layer's tensor that is needed (`need` in the tensor's coordinates, `scale` = 2
-// for the low-resolution lattice of a per-parity / sub-pixel launch, `grow_x` extra columns at the right: the column kernel of a
-// last conv)
-void set_window(SplitArgs& a, const Rect& need, int scale = 1, int grow_x = 0) {
-    if (!need.on) return;
-    a.wy0 = need.y0 / scale; a.wx0 = need.x0 / scale;
-    a.wy1 = std::min(a.Hout, (need.y1 + scale - 1) / scale);
-    a.wx1 = std::min(a.Wout, (need.x1 + scale - 1) / scale + grow_x);
-    a.wy1 = std::max(a.wy1, a.wy0 + 1); a.wx1 = std::max(a.wx1, a.wx0 + 1);
-    if (a.Dout > 1) {          // plane-stacked 3-D: the planes of the box
-        a.wz0 = std::min(a.Dout - 1, need.z0 / scale);
-        a.Dout = std::max(a.wz0 + 1, std::min(a.Dout, (need.z1 + scale - 1) / scale)) - a.wz0;
-    }
-}
-
-// the FLOP a launch executes of its layer's: the share of the lattice that lies in its window
-double window_flops(const SplitArgs& a, double flops) {
-    flops *= (double)(a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout);
-    if (a.Dlat > 0) flops *= (double)a.Dout / a.Dlat;
-    return flops;
-}
-
+// the lattice of a 2xf16 launch as split_args left it
+Dhw lattice(const SplitArgs& a) { return {a.Dout, a.Hout, a.Wout}; }
 
 // the weights-resident kernel (conv_rw.h) for a 3x3 32 -> 32 layer: window and tile grid as launch_split, one persistent
 // workgroup per CU
-int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops) {
+int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops, const Window& w) {
     static char names[3][3][96];
     const int di = dil == 1 ? 0 : dil == 2 ? 1 : 2;
     if (!names[di][epi][0])
         snprintf(names[di][epi], sizeof names[di][epi], "conv_split_rw_kernel<K=3x3,D=%d,MT=32,EPI=%d> (weights resident)", dil, epi);
-    flops = window_flops(a, flops);
-    a.tiles_x = (a.wx1 - a.wx0 + 31) / 32;
-    a.tiles_y = (a.wy1 - a.wy0 + 8 * dil - 1) / (8 * dil) * dil;
+    flops *= window_share(w, lattice(a));
+    apply_window(a, w);
+    a.tiles_x = tile_count(w.x1 - w.x0, 32);
+    a.tiles_y = tile_count(w.y1 - w.y0, 8, dil);
     const long long nt = (long long)a.tiles_x * a.tiles_y;
     if (nt >= (1LL << 30)) return fail(ctx, "conv grid too large");
     a.n_tiles = (int)nt;
@@ -242,7 +250,8 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
     if (sres && L.dims == 3) a.Dres = sres->D;
     a.n_chunks = rt.s_n_chunks;
     a.cog_inner = L.head ? rt.s_n_cog : 1;
-    double flops = 2.0 * L.cout * L.cin * std::pow((double)L.k, L.dims) * (double)dst.D * a.Hout * a.Wout;
+    double flops = conv_flops(L.cout, L.cin, L.k, L.dims, {dst.D, lat.H, lat.W});
+    const Window w = launch_window(dst.need, lattice(a));      // (a pooled dst keeps its need in the coordinates of the un-pooled conv output)
     if (fold) {
         // out(y, x) += proj(h)(y + res_crop, x + res_crop); the centre tap of output y sits at tile-input row y - pad + (k/2) dil
         a.in2 = reinterpret_cast<const uint4*>(fold->p);
@@ -253,16 +262,14 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
         a.in2_oy = a.in2_ox = L.res_crop + L.pad - (L.k / 2) * L.dil;
         a.n_chunks = rt.f_n_chunks;
         flops += 2.0 * L.cout * (8.0 * rt.fold_cells) * (double)a.Hout * a.Wout;
-        set_window(a, dst.need);
-        return launch_split(ctx, ks, a, rt.f_n_cog, flops);
+        return launch_split(ctx, ks, a, rt.f_n_cog, flops, w);
     }
-    set_window(a, dst.need);           // (a pooled dst keeps its need in the coordinates of the un-pooled conv output)
     if (rt.d_w_rw && !pooled && !s2 && !ctx->rec_on && ks.epi <= EPI_RES_POST && L.dims == 2 && ctx->rw_enabled) {
         a.wpk = reinterpret_cast<const uint4*>(rt.d_w_rw);
         a.wscale = rt.d_ws_rw;
-        return launch_rw(ctx, a, L.dil, ks.epi, flops);
+        return launch_rw(ctx, a, L.dil, ks.epi, flops, w);
     }
-    return launch_split(ctx, ks, a, rt.s_n_cog, flops);
+    return launch_split(ctx, ks, a, rt.s_n_cog, flops, w);
 }
 
 namespace {
@@ -287,10 +294,11 @@ const SplitStep* split_plan(tpz_ctx* ctx, const SplitKernelInfo& ks, const Split
     return d;
 }
 
-int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops) {
-    flops = window_flops(a, flops);
-    a.tiles_x = (a.wx1 - a.wx0 + ks.TW - 1) / ks.TW;
-    a.tiles_y = (a.wy1 - a.wy0 + ks.TH * ks.D - 1) / (ks.TH * ks.D) * ks.D;
+int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_cog, double flops, const Window& w) {
+    flops *= window_share(w, lattice(a));
+    apply_window(a, w);
+    a.tiles_x = tile_count(w.x1 - w.x0, ks.TW);
+    a.tiles_y = tile_count(w.y1 - w.y0, ks.TH, ks.D);
     a.xcd_swizzle = 1;
     a.issuer_half = ks.WAVES == 8 && ks.MT >= 96 && !ctx->dbg.no_issuer;   // -3 .. -4 % on the 128-channel tiles, nothing at 64 (tools/split_ablate.hip)
     if (a.KZ < 1) { a.KZ = 1; a.pad_z = 0; a.Din = a.Dout = a.Dfull = a.Dres = 1; a.ooz = 0; }     // 2-D launch
@@ -396,8 +404,7 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.out = reinterpret_cast<uint4*>(dst.p);
         a.n_chunks = sp.n_chunks_low;
         const double fl = 2.0 * L.cout * (ph.c1 * 9.0 * 4.0 + 25.0 * 4.0) * (double)s1.H * s1.W;
-        set_window(a, dst.need, 2);
-        const int rc = launch_split(ctx, *sp.ks_sub, a, sp.n_cog_sub, fl);
+        const int rc = launch_split(ctx, *sp.ks_sub, a, sp.n_cog_sub, fl, launch_window(dst.need, lattice(a), 2));
         pool_release(ctx, X);
         return rc;
     }
@@ -434,8 +441,8 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.slope = 1.f;
         a.n_chunks = 1;
         a.cog_inner = 1;
-        const double fl = 2.0 * L.cout * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
-        if (launch_mfma(ctx, *sp.ki_skip_stem, a, 1, fl)) return 1;
+        // (over the whole grid, whatever is needed of it)
+        if (launch_mfma(ctx, *sp.ki_skip_stem, a, 1, conv_flops(L.cout, 1, L.k, L.dims, dhw(dst)), launch_window(Rect(), dhw(dst)))) return 1;
     } else {
         SplitArgs a = split_args(ctx, s2.p, (int)split_cells(s2.C), dhw(s2), L.cout, dhw(dst), 1, dhw(dst), L.dims == 3 ? L.k : 0,
                                  L.pad, 1.f);
@@ -444,9 +451,10 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.bias = bias_view(ctx, rt.d_bias);
         a.out = reinterpret_cast<uint4*>(dst.p);
         a.n_chunks = sp.n_chunks_skip;
-        const double fl = 2.0 * L.cout * ph.c2 * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
-        set_window(a, dst.need);       // (even-aligned by need_regions: the parity launch below adds itself in place)
-        if (launch_split(ctx, *sp.ks_skip, a, sp.n_cog_skip, fl)) return 1;
+        // (the window is even-aligned by need_regions: the parity launch below adds itself in place)
+        if (launch_split(ctx, *sp.ks_skip, a, sp.n_cog_skip, conv_flops(L.cout, ph.c2, L.k, L.dims, dhw(dst)),
+                         launch_window(dst.need, lattice(a))))
+            return 1;
     }
     // ---- every output parity over the low-resolution source in one launch, added in place, then the activation
     {
@@ -475,10 +483,9 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.Hres = dst.H; a.Wres = dst.W;
         if (L.dims == 3) a.Dres = dst.D;
         a.n_chunks = sp.n_chunks_low;
-        const double fl = 2.0 * L.cout * ph.c1 * std::pow((double)ph.k1, L.dims) * (double)s1.D * s1.H * s1.W * (1 << L.dims);
+        const double fl = conv_flops(L.cout, ph.c1, ph.k1, L.dims, dhw(s1)) * (1 << L.dims);
         const SplitKernelInfo& kk = sp.ks_sub ? *sp.ks_sub : (sp.low_with_skip ? *sp.ks_low_plain : *sp.ks_low);
-        set_window(a, dst.need, 2);
-        const int rc = launch_split(ctx, kk, a, sp.ks_sub ? sp.n_cog_sub : sp.n_cog_low, fl);
+        const int rc = launch_split(ctx, kk, a, sp.ks_sub ? sp.n_cog_sub : sp.n_cog_low, fl, launch_window(dst.need, lattice(a), 2));
         if (Xs2d) pool_release(ctx, Xs2d);
         if (rc) return 1;
     }
@@ -496,13 +503,14 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
     const int Hc = layer_out_dhw(L, dhw(s1)).H, Wc = layer_out_dhw(L, dhw(s1)).W;      // (dilation 1: prepare_split)
     float* X = (float*)pool_alloc(ctx, (size_t)ncell * 8 * rows * Wc * sizeof(float));
     if (!X) return fail(ctx, "out of device memory");
+    // the window of the conv (dst.need: in the coordinates of the conv output, also when the max-pool is fused)
+    const Window w = launch_window(dst.need, {dst.D, Hc, Wc});
     // (2-D with a window: only the rows and columns the windowed conv reads -- output row y reads input rows y - pad .. y + pad)
-    const Rect& w = dst.need;
     hipError_t e;
     {
         const float* sp_ = s1.p; unsigned* fl_ = ctx->d_flag;
         const int k = L.k, pad = L.pad, W1 = s1.W;
-        if (w.on && L.dims == 2) {
+        if (dst.need.on && L.dims == 2) {
             const size_t r0 = (size_t)std::max(0, w.y0 - L.pad), r1 = (size_t)std::min(s1.H, w.y1 + L.pad);
             const int c0 = w.x0, c1 = std::min(Wc, (w.x1 + 1) & ~1);
             e = enqueue(ctx, [=](hipStream_t st) { return launch_shiftx_split(sp_, X, k, pad, rows, W1, Wc, fl_, st, r0, r1, c0, c1); });
@@ -519,9 +527,7 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
     a.bias = bias_view(ctx, rt.d_bias);
     a.out = reinterpret_cast<uint4*>(dst.p);
     a.n_chunks = rt.s_n_chunks;
-    const double fl = 2.0 * L.cout * std::pow((double)L.k, L.dims) * (double)dst.D * Hc * Wc;
-    set_window(a, dst.need);
-    const int rc = launch_split(ctx, ks, a, rt.s_n_cog, fl);
+    const int rc = launch_split(ctx, ks, a, rt.s_n_cog, conv_flops(L.cout, 1, L.k, L.dims, {dst.D, Hc, Wc}), w);
     pool_release(ctx, X);
     return rc;
 }
@@ -531,15 +537,13 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
 int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, const float* d_nrm, int norm_out,
                    const Slot* sres = nullptr) {
     const tpz_layer& L = rt.L;
+    const Window w = launch_window(dst.need, dhw(dst));       // what is needed of the output
     if (rt.d_wlast) {
         // one pass: stencil + bias + residual + un-normalisation (conv_cout1_split_kernel)
-        const Rect& w = dst.need;
-        const int z0 = w.on ? w.z0 : 0, z1 = w.on ? std::min(dst.D, w.z1) : dst.D;
-        const int y0 = w.on ? w.y0 : 0, y1 = w.on ? std::min(dst.H, w.y1) : dst.H;
-        const int x0 = w.on ? w.x0 : 0, x1 = w.on ? std::min(dst.W, w.x1) : dst.W;
+        const int z0 = w.z0, z1 = w.z1, y0 = w.y0, y1 = w.y1, x0 = w.x0, x1 = w.x1;
         const double vox = (double)(z1 - z0) * (y1 - y0) * (x1 - x0);
         const double taps = std::pow((double)L.k, L.dims);
-        const double fl = 2.0 * L.cin * taps * vox;
+        const double fl = conv_flops(1, L.cin, L.k, L.dims, {z1 - z0, y1 - y0, x1 - x0});
         // algorithmic bytes: the input box (with its halo) once, the output (and the residual) once, the weights once
         const double by = 32.0 * split_cells(s1.C) * (double)std::min(dst.D, z1 - z0 + (L.dims == 3 ? 2 * L.pad : 0)) *
                               std::min(dst.H, y1 - y0 + 2 * L.pad) * std::min(dst.W, x1 - x0 + 2 * L.pad) +
@@ -568,21 +572,19 @@ int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, c
     a.wscale = rt.d_wscale;
     a.out_f32 = Y;
     a.n_chunks = rt.s_n_chunks;
-    const double fl = 2.0 * L.cin * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
-    const Rect& w = dst.need;
-    set_window(a, w, 1, 2 * L.pad);       // Y columns x .. x + k - 1 feed output column x
-    int rc = launch_split(ctx, ks, a, rt.s_n_cog, fl);
+    Window wy = w;
+    wy.x1 += 2 * L.pad;                   // Y columns x .. x + k - 1 feed output column x
+    int rc = launch_split(ctx, ks, a, rt.s_n_cog, conv_flops(1, L.cin, L.k, L.dims, dhw(dst)), wy);
     if (!rc) {
         // (labelled: an HBM-bound kernel whose bandwidth bench.py reports -- reads k planes of Wp columns, writes one of W)
-        const double ss_rows = w.on ? (double)(w.y1 - w.y0) * (L.dims == 3 ? w.z1 - w.z0 : 1) : (double)rows, ss_cols = w.on ? (double)(w.x1 - w.x0) : (double)dst.W;
+        const double ss_rows = (double)(w.y1 - w.y0) * (w.z1 - w.z0), ss_cols = (double)(w.x1 - w.x0);
         // (a residual of the output's own size -- UDenoiseNet3: x - dec1(h), weights negated -- is added here, in fp32)
         const float* resp = sres ? sres->p : nullptr;
         float* dp_ = dst.p;
         const int k = L.k, Wd = dst.W;
         const float b0 = L.b_off >= 0 ? rt.bias0 : 0.f;
-        const size_t r0 = w.on ? (size_t)w.y0 : 0, r1 = w.on ? (size_t)w.y1 : (size_t)-1;
-        const int c0 = w.on ? w.x0 : 0, c1 = w.on ? w.x1 : 0x7fffffff;
-        const int Hp = (w.on && L.dims == 3) ? dst.H : 0, z0 = w.z0, z1 = std::min(dst.D, w.z1);
+        const size_t r0 = (size_t)w.y0, r1 = (size_t)w.y1;
+        const int c0 = w.x0, c1 = w.x1, Hp = dst.H, z0 = w.z0, z1 = w.z1;
         hipError_t e = enqueue(ctx, 2, 0.0, "shiftsum (last conv: sum of the k column-kernel planes + bias + un-normalisation)",
                                4.0 * ss_rows * ((double)L.k * (ss_cols + 2 * L.pad) + ss_cols), [=](hipStream_t st) {
                                    return launch_shiftsum(Y, dp_, k, rows, Wd, Wp, b0, d_nrm, norm_out, st, r0, r1, c0, c1, resp, Hp, z0, z1);
@@ -613,6 +615,29 @@ float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
     if (e != hipSuccess) { pool_release(ctx, q); return nullptr; }
     s.alt = q;
     return q;
+}
+// ... the slot as a source in that format; .p == nullptr: the conversion failed
+Slot source_view(tpz_ctx* ctx, Slot& s, bool want_split) {
+    Slot v = s;
+    v.p = slot_as(ctx, s, want_split);
+    v.split = want_split;
+    return v;
+}
+
+// Gives layer i its destination: C channels of `o` voxels as fp32 planes or (split) as split cells, which take the bytes of fp32
+// with the channels rounded up to whole 8-channel cells -- d_out for the last layer, else a buffer of the workspace pool that the
+// slot owns.  `need`: the part of the tensor anything reads.
+int make_dst(tpz_ctx* ctx, Slot& dst, int i, bool last, float* d_out, int C, bool split, const Dhw& o, const Rect& need) {
+    const size_t c_alloc = split ? split_cells(C) * 8 : (size_t)C;
+    float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * o.H * o.W * sizeof(float));
+    if (!p) return fail(ctx, "out of device memory (layer %d)", i);
+    set_dense(dst, p, C, o.D, o.H, o.W);
+    dst.need = need;
+    dst.split = split;
+    dst.pooled = false;
+    dst.alt = nullptr;
+    dst.owned = !last;
+    return 0;
 }
 
 int run_conv(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* s2, const Slot* sres, Slot& dst,
@@ -649,28 +674,29 @@ int run_conv(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* s2, co
     a.slope = L.slope;
     if (L.head) { a.head_out = dst.p; a.out = nullptr; }
     else a.out = dst.p;
-    set_window(a, dst.need);          // patched / tiled denoise: only what the kept centre depends on (need_regions)
-    const double flops = 2.0 * L.cout * L.cin * std::pow((double)L.k, L.dims) * (double)dst.D * dst.H * dst.W;
+    // patched / tiled denoise: only what the kept centre depends on (need_regions)
+    const Window w = launch_window(dst.need, dhw(dst), 1, FP32_ALIGN_X);
+    const double flops = conv_flops(L.cout, L.cin, L.k, L.dims, dhw(dst));
     if (rt.ki) {
         const ConvKernelInfo& ki = split_out ? *rt.ki_stem_split : *rt.ki;    // same tile and weight packing
         a.flag = ctx->d_flag;
         const LayerRT::Phase& ph = rt.phase;
         if (ph.valid && s2 && s1.C == ph.c1 && s2->C == ph.c2 && s2->H == 2 * s1.H && s2->W == 2 * s1.W &&
             (L.dims == 2 || s2->D == 2 * s1.D))
-            return run_conv_phases(ctx, rt, a, s1, *s2, dst);
+            return run_conv_phases(ctx, rt, a, s1, *s2, dst, w);
         if (s2 && (s1.C % ki.NCH) != 0)
             return fail(ctx, "fused concat needs the first source's channels (%d) to be a multiple of %d", s1.C, ki.NCH);
         a.n_chunks = rt.n_chunks;
         a.cog_inner = rt.cog_inner;
-        if (launch_mfma(ctx, ki, a, rt.n_cog, flops)) return 1;
+        if (launch_mfma(ctx, ki, a, rt.n_cog, flops, w)) return 1;
     } else {
         if (s1.D != geo.D || s1.H != geo.H || s1.W != geo.W) return fail(ctx, "direct conv cannot upsample");
+        apply_window(a, w);
         const ConvArgs ac = a;
         const float* wp_ = rt.d_wpk;
         const int k = L.k, kz = L.dims == 3 ? L.k : 1, dil = L.dil;
-        hipError_t e = enqueue(ctx, 1, a.wy1 > 0 ? flops * (a.wy1 - a.wy0) * (a.wx1 - a.wx0) / ((double)a.Hout * a.Wout) *
-                                                       (a.wz1 > 0 ? (double)(a.wz1 - a.wz0) / a.Dout : 1.0) : flops, nullptr,
-                               0.0, [=](hipStream_t st) { return launch_conv_direct(ac, wp_, k, kz, dil, st); });
+        hipError_t e = enqueue(ctx, 1, flops * window_share(w, dhw(dst)), nullptr, 0.0,
+                               [=](hipStream_t st) { return launch_conv_direct(ac, wp_, k, kz, dil, st); });
         HIPCHK(ctx, e);
     }
     return 0;
@@ -831,6 +857,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
     slots.resize(std::max<size_t>(slots.size(), (size_t)m->n_slots));
     std::vector<Rect> need;
     if (keep && slots[0].set) need = need_regions(m, slots[0].D, slots[0].H, slots[0].W, *keep, split);
+    auto need_of = [&](int slot) { return need.empty() ? Rect() : need[slot]; };
     int rc = 0;
     for (int i = 0; i < nl && rc == 0; ++i) {
         const LayerRT& rt = m->layers[i];
@@ -861,26 +888,16 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
                 rc = fail(ctx, "layer %d: residual geometry mismatch", i);
                 break;
             }
-            // a fused max-pool: the slot receives the pooled tensor
-            const int Hd = pl.fuse_pool ? o.H / 2 : o.H, Wd = pl.fuse_pool ? o.W / 2 : o.W;
-            // split tensors take the bytes of fp32 with the channels rounded up to whole 8-channel cells
-            const size_t c_alloc = pl.split_dst ? split_cells(Co) * 8 : (size_t)Co;
-            float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * Hd * Wd * sizeof(float));
-            if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
-            if (pl.fuse_pool && (Hd < 1 || Wd < 1)) { rc = fail(ctx, "layer %d: input too small to pool", i + 1); break; }
-            set_dense(dst, p, Co, o.D, Hd, Wd);
-            dst.need = need.empty() ? Rect() : need[L.dst];
-            dst.split = pl.split_dst;
+            // a fused max-pool: the slot receives the pooled tensor (and keeps its need in the coordinates of the conv output)
+            const Dhw od = {o.D, pl.fuse_pool ? o.H / 2 : o.H, pl.fuse_pool ? o.W / 2 : o.W};
+            if (pl.fuse_pool && (od.H < 1 || od.W < 1)) { rc = fail(ctx, "layer %d: input too small to pool", i + 1); break; }
+            if ((rc = make_dst(ctx, dst, i, last, d_out, Co, pl.split_dst, od, need_of(L.dst)))) break;
             dst.pooled = pl.fuse_pool;
-            dst.alt = nullptr;
-            dst.owned = !last;
             if (pl.split_dst && last) { rc = fail(ctx, "layer %d: the result must leave as fp32", i); break; }
             // sources in the format the chosen kernels read (converted once if the producer wrote the other one)
-            Slot v1 = s1, v2, vres;
-            v1.p = slot_as(ctx, slots[L.src], pl.split1);
-            v1.split = pl.split1;
-            if (s2) { v2 = *s2; v2.p = slot_as(ctx, slots[L.src2], pl.split2); v2.split = pl.split2; }
-            if (sres) { vres = *sres; vres.p = slot_as(ctx, slots[L.res], pl.split_res); vres.split = pl.split_res; }
+            const Slot v1 = source_view(ctx, slots[L.src], pl.split1);
+            const Slot v2 = s2 ? source_view(ctx, slots[L.src2], pl.split2) : Slot();
+            const Slot vres = sres ? source_view(ctx, slots[L.res], pl.split_res) : Slot();
             if (!v1.p || (s2 && !v2.p) || (sres && !vres.p)) { rc = fail(ctx, "layer %d: tensor format conversion failed", i); break; }
             // slot 0 arrives already normalised (denoise_region); only the last layer un-normalises
             const int norm_out = (d_nrm && last) ? 1 : 0;
@@ -889,9 +906,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             case FORM_LAST: rc = run_last_split(ctx, rt, v1, dst, d_nrm, norm_out, sres ? &vres : nullptr); break;
             case FORM_PARITY: rc = run_conv_split_phases(ctx, rt, v1, v2, dst); break;
             case FORM_SPLIT_FOLD: {
-                Slot vf = slots[rt.fold_src];
-                vf.p = slot_as(ctx, slots[rt.fold_src], true);
-                vf.split = true;
+                const Slot vf = source_view(ctx, slots[rt.fold_src], true);
                 if (!vf.p) rc = fail(ctx, "layer %d: tensor format conversion failed", i);
                 else rc = run_conv_split(ctx, rt, v1, nullptr, dst, nullptr, false, &vf);
                 break;
@@ -902,15 +917,9 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             }
         } else if (L.op == TPZ_OP_MAXPOOL2 && s1.pooled && L.dims == 3) {
             // pooled in-plane by the producing conv: the z pairs remain
-            const int Do = s1.D / 2;
-            if (Do < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
-            float* p = last ? d_out : (float*)pool_alloc(ctx, split_cells(s1.C) * 8 * (size_t)Do * s1.H * s1.W * sizeof(float));
-            if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
             const Slot src = s1;
-            set_dense(dst, p, src.C, Do, src.H, src.W);
-            dst.split = true;
-            dst.alt = nullptr;
-            dst.owned = !last;
+            if (src.D / 2 < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
+            if ((rc = make_dst(ctx, dst, i, last, d_out, src.C, true, {src.D / 2, src.H, src.W}, need_of(L.dst)))) break;
             hipError_t e;
             {
                 const float* sp_ = src.p; float* dp_ = dst.p;
@@ -921,7 +930,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
         } else if (L.op == TPZ_OP_MAXPOOL2 && s1.pooled) {
             // already pooled by the producing conv: the slot changes hands
             dst = s1;
-            dst.need = need.empty() ? Rect() : need[L.dst];
+            dst.need = need_of(L.dst);
             dst.pooled = false;
             slots[L.src].owned = false;
             slots[L.src].alt = nullptr;
@@ -932,14 +941,8 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             const bool sp = s1.split && !last;                // pooled in the format the source has
             const float* src_p = s1.p;
             if (s1.split && !sp) { src_p = slot_as(ctx, slots[L.src], false); if (!src_p) { rc = fail(ctx, "conversion failed"); break; } }
-            const size_t c_alloc = sp ? split_cells(s1.C) * 8 : (size_t)s1.C;
-            float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * o.H * o.W * sizeof(float));
-            if (!p) { rc = fail(ctx, "out of device memory (layer %d)", i); break; }
             const int Cs = s1.C, Ds = s1.D, Hs = s1.H, Ws = s1.W;
-            set_dense(dst, p, Cs, o.D, o.H, o.W);
-            dst.split = sp;
-            dst.alt = nullptr;
-            dst.owned = !last;
+            if ((rc = make_dst(ctx, dst, i, last, d_out, Cs, sp, o, need_of(L.dst)))) break;
             float* dp_ = dst.p;
             const int k = L.k, dil = L.dil, dims = L.dims, pad = L.pad;
             const bool by2 = L.op == TPZ_OP_MAXPOOL2, padded = is_padded_pool(L), mean = L.op == TPZ_OP_AVGPOOL;

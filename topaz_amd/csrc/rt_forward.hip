@@ -26,9 +26,8 @@ int model_halo(const tpz_model* m) {
     int h = 0;
     for (const LayerRT& rt : m->layers) {
         const tpz_layer& L = rt.L;
-        if (L.op == TPZ_OP_CONV) h += std::max(L.pad, L.dil * (L.k - 1) - L.pad);        // (an upper bound: every layer counted)
-        else if (L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) h += std::max(L.pad, L.dil * (L.k - 1) - L.pad);
-        else return -1;                                                                   // (pooling by 2: not equivariant)
+        if (L.op != TPZ_OP_CONV && L.op != TPZ_OP_MAXPOOL && L.op != TPZ_OP_AVGPOOL) return -1;      // (pooling by 2: not equivariant)
+        h += std::max(L.pad, L.dil * (L.k - 1) - L.pad);                 // (an upper bound: every conv and pool counted)
     }
     return (h + 1) & ~1;
 }
@@ -108,7 +107,7 @@ int tpz_model_forward(tpz_model* m, const float* d_in, int n, int D, int H, int 
         bool done = false;
         if (m->split_ok && !ctx->exact && split_volume_fits(m, D, H, W)) {
             // 2xf16 path; an activation beyond the f16 range (flag) sends this image to the fp32 kernels instead
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream));
+            HIPCHK(ctx, flag_clear(ctx));
             float* x_b = const_cast<float*>(d_in) + (size_t)b * D * H * W;
             // RANGE SCALING (scoring networks = programs ending in the linear head): `topaz extract` does not normalise its
             // input (extract.py:234-249), and a raw-count micrograph would leave the f16 range in the stem.  The network is
@@ -142,9 +141,9 @@ int tpz_model_forward(tpz_model* m, const float* d_in, int n, int D, int H, int 
                 const float hb = m->layers.back().head_b;
                 HIPCHK(ctx, enqueue(ctx, [=](hipStream_t st) { return launch_unscale(out_b, n_out, rng, hb, st); }));
             }
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            done = (*ctx->h_flag == 0);
+            unsigned overflow = 0;
+            HIPCHK(ctx, flag_read(ctx, &overflow));
+            done = (overflow == 0);
             if (done) ++m->n_split; else ++m->n_fallback;
         }
         if (!done && run_image(m, const_cast<float*>(d_in) + (size_t)b * D * H * W, D, H, W, out_b, Co, Do, Ho, Wo, false)) return 1;
@@ -195,16 +194,16 @@ int tpz_conv_split_2d(tpz_ctx* ctx, const float* d_in, int cin, int H, int W, co
         if (!x_s || !y_s || (d_res && !r_s)) rc = fail(ctx, "out of device memory");
     }
     if (!rc) {
-        (void)hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream);
+        (void)flag_clear(ctx);
         (void)launch_to_split(d_in, x_s, cin, H, W, ctx->d_flag, ctx->stream);
         set_dense(s1, x_s, cin, 1, H, W); s1.split = true;
         if (d_res) { (void)launch_to_split(d_res, r_s, cout, Hr, Wr, ctx->d_flag, ctx->stream); set_dense(sres, r_s, cout, 1, Hr, Wr); sres.split = true; }
         set_dense(dst, L.head ? d_out : y_s, L.head ? 1 : cout, 1, Ho, Wo);
         rc = run_conv_split(ctx, rt, s1, d_res ? &sres : nullptr, dst);
         if (!rc && !L.head) (void)launch_from_split(y_s, d_out, cout, Ho, Wo, ctx->stream);
-        (void)hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "tpz_conv_split_2d: kernel failed");
-        if (overflow) *overflow = (int)*ctx->h_flag;
+        unsigned flag = 0;
+        if (flag_read(ctx, &flag, false) != hipSuccess) rc = fail(ctx, "tpz_conv_split_2d: kernel failed");
+        if (overflow) *overflow = (int)flag;
     }
     if (x_s) pool_release(ctx, x_s);
     if (y_s) pool_release(ctx, y_s);
@@ -290,15 +289,15 @@ int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, in
         float* y_s = (float*)pool_alloc(ctx, split_cells(C) * 8 * (size_t)Do * Ho * Wo * 4);
         if (!x_s || !y_s) rc = fail(ctx, "out of device memory");
         if (!rc) {
-            hipError_t e = hipMemsetAsync(ctx->d_flag, 0, sizeof(unsigned), ctx->stream);
+            hipError_t e = flag_clear(ctx);
             if (e == hipSuccess) e = launch_to_split(d_in, x_s, C, D * H, W, ctx->d_flag, ctx->stream);
             if (e == hipSuccess) e = launch_pool_pad(x_s, y_s, C, D, H, W, dil, pad, dims, mean, true, ctx->stream);
             if (e == hipSuccess) e = launch_from_split(y_s, d_out, C, Do * Ho, Wo, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_flag, ctx->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
             if (e != hipSuccess) rc = fail(ctx, "tpz_pool: launch failed: %s", hipGetErrorString(e));
         }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");
-        if (!rc && overflow) *overflow = (int)*ctx->h_flag;
+        unsigned flag = 0;
+        if (flag_read(ctx, &flag) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");
+        if (!rc && overflow) *overflow = (int)flag;
         if (x_s) pool_release(ctx, x_s);
         if (y_s) pool_release(ctx, y_s);
         return rc;

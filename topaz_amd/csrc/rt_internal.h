@@ -8,8 +8,9 @@
 //   rt_load.hip     model loading: the kernels each layer CAN run on and their weight packs (fp32 and 2xf16 forms, per-parity
 //                   decoder forms, folded projections), zero-padded widths, the bias arena
 //   rt_exec.hip     the layer-program executor: conv_plan() -- the one place that says which of those kernels a conv layer
-//                   DOES run on, in which tensor formats (ConvForm / ConvPlan below) --, launchers, per-layer drivers, the
-//                   backward walk of the windows (need_regions)
+//                   DOES run on, in which tensor formats (ConvForm / ConvPlan below) --, the launch window (launch_window, with
+//                   its FLOP share and tile grid), launchers, per-layer drivers, the backward walk of the windows
+//                   (need_regions), run_program with its slot helpers (make_dst, source_view)
 //   rt_forward.hip  scoring drivers (range-scaled pass, internal tiling) and the single-op entry points
 //   rt_denoise.hip  the patched 2-D and tiled 3-D denoising drivers (batched passes over the lanes)
 //   rt_stats.hip    mean / std, GMM fit, affine, normalise
@@ -205,6 +206,10 @@ int fail(tpz_ctx* ctx, const char* fmt, ...);
 // ---- rt_core.hip
 void* pool_alloc(tpz_ctx* ctx, size_t bytes);
 void pool_release(tpz_ctx* ctx, void* p);
+hipError_t flag_clear(tpz_ctx* ctx);       // the f16-range overflow flag of a 2xf16 pass (d_flag): zero it on the ctx stream ...
+// ... copy it back, wait for the stream and return it in *flag.  The error is the copy's, else the wait's; check_copy = false: the
+// wait's alone (tpz_conv_split_2d, which checks none of its launches)
+hipError_t flag_read(tpz_ctx* ctx, unsigned* flag, bool check_copy = true);
 float* next_nrm(tpz_ctx* ctx);
 int lanes_begin(tpz_ctx* ctx);
 void lane_enter(tpz_ctx* ctx, int k);
