@@ -143,6 +143,25 @@ int tpz_mean_std(tpz_ctx* ctx, const float* d_x, size_t n, int unbiased, float* 
 int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, const double* splits, int n_init,
                 double alpha, double beta, double scale, int num_iters, double tol, double* mus, double* stds,
                 double* pis_out, double* logps);
+/* tpz_gmm_fit with all initialisations advanced together: one pass over the pixels per EM iteration serves every
+ * initialisation that has not converged yet (one launch pair, one download, one synchronise), instead of one pass per
+ * initialisation and iteration.  Every initialisation's sums are accumulated in the order tpz_gmm_fit accumulates them, so the
+ * four output arrays equal tpz_gmm_fit's bit for bit.  *n_passes (may be NULL) receives the number of passes over d_x:
+ * at most num_iters + 3 (moments, hard split, first E-step, the EM iterations). */
+int tpz_gmm_fit_fused(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, const double* splits, int n_init,
+                      double alpha, double beta, double scale, int num_iters, double tol, double* mus, double* stds,
+                      double* pis_out, double* logps, int* n_passes);
+/* Exact order statistics: h_out[j] = the h_ranks[j]-th smallest (0-based) of the n device floats d_x, for 1 <= k <= 32 ranks in
+ * one call -- what np.partition / np.quantile's bracketing elements are.  Radix select on the order-preserving integer key of a
+ * float, four 8-bit digits, integer counts (independent of scheduling); -0 sorts before +0.  If any input is NaN every output
+ * is NaN (np.quantile).  A rank outside [0, n) is an error.  h_ranks / h_out on the host; synchronises. */
+int tpz_order_stats(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h_ranks, int k, float* h_out);
+/* d_out[i] = d_x[h_idx[i]], i < m: the sub-sample of `topaz normalize --sample`.  The m indices are on the host and uploaded by
+ * the call; one outside [0, n) is an error, raised before anything is launched.  Asynchronous. */
+int tpz_gather_f32(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h_idx, size_t m, float* d_out);
+/* y = (float)(((double)x - mean) / std): `(x - mu) / std` as numpy evaluates it for a float32 image and np.float64 scalars (the
+ * mixture fit's mu and std) -- the float64 counterpart of tpz_normalize; std == 0 yields inf / nan.  Asynchronous. */
+int tpz_normalize_f64(tpz_ctx* ctx, const float* d_x, size_t n, double mean, double std, float* d_y);
 /* y = x*scale + shift  (the (x-mu)/std and std*y+mu steps of topaz/denoise.py:389,414) */
 int tpz_affine(tpz_ctx* ctx, const float* d_x, size_t n, float scale, float shift, float* d_y);
 /* y = (x - mean) / std evaluated as numpy does in `(mic - mu) / std` (topaz/denoise.py:389, :412 and commands/normalize):

@@ -53,6 +53,11 @@ _SIGNATURES = {
     'tpz_mean_std': (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     'tpz_gmm_fit': (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double,
                               _P, _P, _P, _P]),
+    'tpz_gmm_fit_fused': (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                    C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int)]),
+    'tpz_order_stats': (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P]),
+    'tpz_gather_f32': (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    'tpz_normalize_f64': (C.c_int, [_P, _P, C.c_size_t, C.c_double, C.c_double, _P]),
     'tpz_affine': (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     'tpz_normalize': (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     'tpz_format_picks': (C.c_longlong, [C.c_char_p, _P, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_longlong]),

@@ -135,17 +135,20 @@ NORMALIZE: List[Flag] = [
     (('files',), dict(nargs='+')),
     (('-s', '--scale'), dict(default=1, type=int, help='shrink the images by this factor first')),
     (('--affine',), dict(action='store_true', help='plain (x - mean) / std of the whole image instead of the mixture fit')),
-    (('--sample',), dict(default=10, type=int, help='fit the mixture on every n-th pixel (random subset)')),
+    (('--sample',), dict(default=10, type=int, help='fit the mixture on every n-th pixel (random subset drawn from the NumPy RNG in '
+                                                    'file order; with --gpus each rank draws for its own files only, so the '
+                                                    'subsets depend on the number of ranks -- --sample 1 does not)')),
     (('--niters',), dict(default=100, type=int, help='cap on the EM iterations of one fit')),
     (('-a', '--alpha'), dict(default=900, type=float, help='alpha of the Beta prior on the mixing proportion')),
     (('-b', '--beta'), dict(default=1, type=float, help='beta of the Beta prior on the mixing proportion')),
     (('--metadata',), dict(action='store_true', help='also write <name>.metadata.json with the fitted parameters')),
     (('-d', '--device'), dict(default=0, type=int, help='GPU to use')),
-    (('-t', '--num-workers'), dict(type=int, default=0, help='accepted for compatibility (the fit runs on the GPU)')),
+    (('-t', '--num-workers'), dict(type=int, default=0, help='accepted for compatibility (the fit runs on the GPU; --gpus shards the files)')),
     (('-j', '--num-threads'), dict(type=int, default=0, help='accepted for compatibility')),
     (('-o', '--destdir'), dict(help='directory to write into')),
     (('--format',), dict(dest='format_', default='mrc', help='comma separated list of mrc, tiff, png')),
     (('-v', '--verbose'), dict(action='store_true', help='name every processed file')),
+    _GPUS,
 ]
 
 

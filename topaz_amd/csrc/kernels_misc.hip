@@ -330,12 +330,6 @@ hipError_t launch_maxpool2_split(const void* in, void* out, int C, int D, int H,
 // torch.std is unbiased (N-1), numpy.std is population (N)  (denoise.py:283 vs :343,:388).
 // sum of squares about a pilot value (the first element) keeps the one-pass variance stable.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void meanstd_partial_kernel(const float* __restrict__ x, int D, int H, int W,
                                                               long long ps, int pitch, double* __restrict__ part) {
     __shared__ double s1[4], s2[4];

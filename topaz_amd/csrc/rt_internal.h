@@ -14,6 +14,8 @@
 //   rt_forward.hip  scoring drivers (range-scaled pass, internal tiling) and the single-op entry points
 //   rt_denoise.hip  the patched 2-D and tiled 3-D denoising drivers (batched passes over the lanes)
 //   rt_stats.hip    mean / std, GMM fit, affine, normalise
+//   rt_preprocess.hip  the preprocess / normalize stream: radix-select order statistics, gather, the GMM fit with all
+//                   initialisations per pass, the float64 normalise (kernels there too)
 //   rt_stage.hip    the staging ring and the host-pointer entry points
 //   rt_nms.hip      the NMS driver
 //   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
@@ -430,6 +432,46 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
                    bool pooled = false, const Slot* fold = nullptr);
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split = false,
                 const Rect* keep = nullptr);
+// ---- the scalar steps of the 2-component mixture fit (topaz/stats.py:87-203), shared by tpz_gmm_fit (rt_stats.hip: one
+// initialisation after the other) and tpz_gmm_fit_fused (rt_preprocess.hip: all of them per pass).  S / T are the seven sums of
+// gmm_pass_kernel, N the number of pixels.
+static inline double beta_logpdf(double x, double a, double b) {
+    // scipy.stats.beta.logpdf: xlog1py(b-1, -x) + xlogy(a-1, x) - betaln(a, b)   (0 * log(0) = 0)
+    const double t1 = (b - 1.0) == 0.0 ? 0.0 : (b - 1.0) * std::log1p(-x);
+    const double t2 = (a - 1.0) == 0.0 ? 0.0 : (a - 1.0) * std::log(x);
+    return t1 + t2 - (std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b));
+}
+struct GmmMoments { double mu_all, var_unbiased; };
+// from the hard pass with split = +inf, which puts everything in component 0
+static inline GmmMoments gmm_moments(const double* S, double N) {
+    const double mu_all = S[3] / N;
+    return {mu_all, (S[5] - 2.0 * mu_all * S[3] + mu_all * mu_all * N) / (N - 1.0)};   // torch .var()
+}
+// single-component model (stats.py:100-103): note the reference adds beta.PDF(1), not its logarithm
+static inline void gmm_single_component(const GmmMoments& M, double N, double alpha, double beta, double scale, double& logp,
+                                        double& mu, double& sd, double& pi) {
+    const double pdf1 = beta == 1.0 ? std::exp(-(std::lgamma(alpha) + std::lgamma(beta) - std::lgamma(alpha + beta)))
+                                    : (beta > 1.0 ? 0.0 : INFINITY);
+    logp = scale * (-(N - 1.0) / 2.0 - N * 0.5 * std::log(2.0 * M_PI * M.var_unbiased)) + pdf1;
+    mu = M.mu_all;
+    sd = std::sqrt(M.var_unbiased);
+    pi = 1.0;
+}
+static inline void gmm_m_step(const double* T, double N, double mu_all, double& mu0, double& mu1, double& var) {
+    mu0 = T[1] > 0 ? T[3] / T[1] : mu_all;
+    mu1 = T[2] > 0 ? T[4] / T[2] : mu_all;
+    var = ((T[5] - 2.0 * mu0 * T[3] + mu0 * mu0 * T[1]) + (T[6] - 2.0 * mu1 * T[4] + mu1 * mu1 * T[2])) / N;
+}
+// MAP estimate of pi under the Beta prior from the assignments of the last E-step
+static inline double gmm_map_pi(const double* S, double N, double alpha, double beta) {
+    const double a_ = alpha + S[2], b_ = beta + N - S[2];
+    return (a_ - 1.0) / (a_ + b_ - 2.0);
+}
+// the parameter block of an E-step pass (gmm_pass_kernel mode 1)
+static inline void gmm_e_step_par(double mu0, double mu1, double var, double pi, double (&par)[6]) {
+    par[0] = mu0; par[1] = mu1; par[2] = var; par[3] = var; par[4] = std::log1p(-pi); par[5] = std::log(pi);
+}
+
 // diag.hip: n_wg 4-wave workgroups each issue 8 * iters v_mfma_f32_16x16x32_f16 per wave on operands read from src (4096 x 16 B);
 // ticks[0] = s_memtime, ticks[1] = s_memrealtime (100 MHz) ticks of wave 0's loop
 hipError_t launch_mfma_spin(const void* src, float* out, int n_wg, int iters, unsigned long long* ticks, hipStream_t s);

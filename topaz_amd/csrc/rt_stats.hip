@@ -1,20 +1,6 @@
 // Statistics and elementwise entry points: mean / std, GMM fit (topaz normalize), affine, normalise.
 #include "rt_internal.h"
 
-namespace tpz::rt {
-namespace {
-
-double beta_logpdf(double x, double a, double b) {
-    // scipy.stats.beta.logpdf: xlog1py(b-1, -x) + xlogy(a-1, x) - betaln(a, b)   (0 * log(0) = 0)
-    const double t1 = (b - 1.0) == 0.0 ? 0.0 : (b - 1.0) * std::log1p(-x);
-    const double t2 = (a - 1.0) == 0.0 ? 0.0 : (a - 1.0) * std::log(x);
-    return t1 + t2 - (std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b));
-}
-
-}  // namespace
-
-}  // namespace tpz::rt
-
 using namespace tpz;
 using namespace tpz::rt;
 
@@ -66,33 +52,22 @@ int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, con
         const double par[6] = {INFINITY, 0, 0, 0, 0, 0};
         if (pass(0, par, S)) rc = fail(ctx, "tpz_gmm_fit: device pass failed");
     }
-    const double mu_all = S[3] / N;
-    const double var_unbiased = (S[5] - 2.0 * mu_all * S[3] + mu_all * mu_all * N) / (N - 1.0);   // torch .var()
+    const GmmMoments M = gmm_moments(S, N);
     for (int i = 0; i < n_init && !rc; ++i) {
         double pi = pis[i];
         if (pi == 1.0) {
-            // single-component model (stats.py:100-103): note the reference adds beta.PDF(1), not its logarithm
-            const double pdf1 = beta == 1.0 ? std::exp(-(std::lgamma(alpha) + std::lgamma(beta) - std::lgamma(alpha + beta)))
-                                            : (beta > 1.0 ? 0.0 : INFINITY);
-            logps[i] = scale * (-(N - 1.0) / 2.0 - N * 0.5 * std::log(2.0 * M_PI * var_unbiased)) + pdf1;
-            mus[i] = mu_all;
-            stds[i] = std::sqrt(var_unbiased);
-            pis_out[i] = 1.0;
+            gmm_single_component(M, N, alpha, beta, scale, logps[i], mus[i], stds[i], pis_out[i]);
             continue;
         }
-        auto m_step = [&](const double (&T)[7], double& mu0, double& mu1, double& var) {
-            mu0 = T[1] > 0 ? T[3] / T[1] : mu_all;
-            mu1 = T[2] > 0 ? T[4] / T[2] : mu_all;
-            var = ((T[5] - 2.0 * mu0 * T[3] + mu0 * mu0 * T[1]) + (T[6] - 2.0 * mu1 * T[4] + mu1 * mu1 * T[2])) / N;
-        };
         double mu0, mu1, var;
         {
             const double par[6] = {splits[i], 0, 0, 0, 0, 0};
             if (pass(0, par, S)) { rc = fail(ctx, "tpz_gmm_fit: device pass failed"); break; }
         }
-        m_step(S, mu0, mu1, var);
+        gmm_m_step(S, N, M.mu_all, mu0, mu1, var);
         auto e_step = [&](double (&T)[7]) -> int {
-            const double par[6] = {mu0, mu1, var, var, std::log1p(-pi), std::log(pi)};
+            double par[6];
+            gmm_e_step_par(mu0, mu1, var, pi, par);
             return pass(1, par, T);
         };
         if (e_step(S)) { rc = fail(ctx, "tpz_gmm_fit: device pass failed"); break; }
@@ -100,9 +75,8 @@ int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, con
         double logp_cur = logp;
         for (int it = 1; it <= num_iters; ++it) {
             // M-step from the assignments of the last E-step (S), MAP estimate of pi under the Beta prior
-            const double a_ = alpha + S[2], b_ = beta + N - S[2];
-            pi = (a_ - 1.0) / (a_ + b_ - 2.0);
-            m_step(S, mu0, mu1, var);
+            pi = gmm_map_pi(S, N, alpha, beta);
+            gmm_m_step(S, N, M.mu_all, mu0, mu1, var);
             if (e_step(S)) { rc = fail(ctx, "tpz_gmm_fit: device pass failed"); break; }
             logp = scale * S[0] + beta_logpdf(pi, alpha, beta);
             if (logp - logp_cur <= tol) break;

@@ -575,6 +575,63 @@ def gmm_fit(x, pis, splits, alpha: float = 900.0, beta: float = 1.0, scale: floa
     return tuple(outs)
 
 
+def gmm_fit_fused(x, pis, splits, alpha: float = 900.0, beta: float = 1.0, scale: float = 1.0, num_iters: int = 100,
+                  tol: float = 1e-3, ctx: Optional[Context] = None):
+    """tpz_gmm_fit_fused: gmm_fit with every initialisation advanced by one pass over the pixels per EM iteration; the same four
+    arrays bit for bit, plus the number of passes over x: (mus, stds, pis, logps, n_passes)."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
+    x = as_device_f32(x.reshape(-1), ctx)
+    pis = np.ascontiguousarray(np.asarray(pis, dtype=np.float64))
+    splits = np.ascontiguousarray(np.asarray(splits, dtype=np.float64))
+    n = len(pis)
+    outs = [np.zeros(n, dtype=np.float64) for _ in range(4)]
+    n_passes = C.c_int(0)
+    check(ctx.lib.tpz_gmm_fit_fused(ctx.handle, _ptr(x), x.numel(), pis.ctypes.data_as(C.c_void_p),
+                                    splits.ctypes.data_as(C.c_void_p), n, float(alpha), float(beta), float(scale),
+                                    int(num_iters), float(tol), *[o.ctypes.data_as(C.c_void_p) for o in outs],
+                                    C.byref(n_passes)), ctx.handle)
+    return tuple(outs) + (int(n_passes.value),)
+
+
+def order_stats(x: torch.Tensor, ranks, ctx: Optional[Context] = None) -> np.ndarray:
+    """tpz_order_stats: the ranks[j]-th smallest (0-based) elements of x, exactly, as a float32 array; at most 32 ranks per call.
+    All NaN when x holds a NaN (np.quantile)."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x.reshape(-1), ctx)
+    ranks = np.ascontiguousarray(np.asarray(ranks, dtype=np.int64).ravel())
+    out = np.zeros(len(ranks), dtype=np.float32)
+    check(ctx.lib.tpz_order_stats(ctx.handle, _ptr(x), x.numel(), ranks.ctypes.data_as(C.c_void_p), len(ranks),
+                                  out.ctypes.data_as(C.c_void_p)), ctx.handle)
+    return out
+
+
+def gather(x: torch.Tensor, idx, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_gather_f32: x.ravel()[idx] on the device; idx: host integers, checked against the size of x before the launch"""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x.reshape(-1), ctx)
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
+    y = torch.empty(len(idx), dtype=torch.float32, device=x.device)
+    check(ctx.lib.tpz_gather_f32(ctx.handle, _ptr(x), x.numel(), idx.ctypes.data_as(C.c_void_p), len(idx), _ptr(y)),
+          ctx.handle)
+    return y
+
+
+def normalize_f64(x: torch.Tensor, mean: float, std: float, ctx: Optional[Context] = None) -> torch.Tensor:
+    """(x - mean) / std as numpy evaluates it for a float32 x and np.float64 scalars (tpz_normalize_f64): in float64, rounded to
+    float32 once; std == 0 -> inf / nan"""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    y = torch.empty_like(x)
+    check(ctx.lib.tpz_normalize_f64(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), _ptr(y)), ctx.handle)
+    return y
+
+
 def maxpool2(x: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     ctx = ctx or get_context()
     ctx.bind_current_stream()

@@ -4,7 +4,11 @@
 The mixture fit itself (`gmm_fit`, stats.py:120-203: twelve initialisations x up to `num_iters` EM iterations over
 the sampled pixels) runs on the device through `tpz_gmm_fit` -- one fused E-step pass per iteration, statistics in
 fp64; the quantile splits and the optional random sub-sample are taken on the host exactly as the reference takes
-them (`np.quantile`, `np.random.choice` on the global NumPy RNG), so a seeded run fits the same pixels."""
+them (`np.quantile`, `np.random.choice` on the global NumPy RNG), so a seeded run fits the same pixels.
+
+That is the per-file path (`Normalize`, `normalize`, `norm_fit`).  `normalize_images`, behind the two commands, streams the files
+through the device instead (second half of this file): the same results byte for byte, with the sub-sample
+gathered, the quantiles selected, all initialisations fitted per pass and the image normalised without leaving the GPU."""
 from __future__ import annotations
 
 import json
@@ -125,13 +129,179 @@ class Normalize:
         return name
 
 
+
+
+# ---- the device-resident stream behind `topaz normalize` / `topaz preprocess` -------------------------------------------------
+# Every pass over the pixels of `Normalize` above, on the device, image after image: ImageFeed decodes the next file into pinned
+# memory while this one is down-sampled, sub-sampled (gather), split at its quantiles (radix select), fitted (all initialisations
+# per pass) and normalised; the result leaves through a pinned ring that a writer thread drains.  `Normalize`, `normalize` and
+# `norm_fit` stay as the per-file path the stream is tested against: same files, byte for byte.
+
+def _quantile_brackets(n: int, q):
+    """np.quantile's `linear` method for n sorted values: the positions of the two bracketing order statistics and the weight
+    gamma of each quantile, formed as numpy forms them (virtual index (n - 1) q; at the upper end both positions are the last
+    element).  q: float64 in [0, 1]."""
+    q = np.asarray(q, dtype=np.float64)
+    if q.size and not (np.all(q >= 0) and np.all(q <= 1)):
+        raise ValueError('Quantiles must be in the range [0, 1]')
+    virtual = (n - 1) * q
+    previous = np.floor(virtual)
+    following = previous + 1
+    above = virtual >= n - 1
+    previous[above] = -1
+    following[above] = -1
+    gamma = virtual - previous
+    return previous.astype(np.intp) % n, following.astype(np.intp) % n, gamma
+
+
+def _lerp_quantiles(a, b, gamma):
+    """numpy's interpolation between the bracketing values a <= b (float32) with float64 weights: a + (b - a) t below t = 0.5,
+    b - (b - a)(1 - t) from there on, hence a where a == b; b - a is formed in the dtype of the values, as numpy forms it."""
+    a, b = np.asarray(a), np.asarray(b)
+    diff = np.subtract(b, a)
+    out = np.asarray(np.add(a, diff * gamma), dtype=np.float64)
+    np.subtract(b, diff * (1 - gamma), out=out, where=gamma >= 0.5)
+    return out
+
+
+def quantiles_device(x_dev, q):
+    """np.quantile(x, q) (default `linear` method, float64 result) of a device tensor without sorting or downloading it: the
+    bracketing order statistics of all quantiles come from one radix select (runtime.order_stats), the interpolation is numpy's,
+    on the host.  NaN everywhere when x holds a NaN."""
+    from . import runtime as rt
+    q = np.asarray(q, dtype=np.float64)
+    lo, hi, gamma = _quantile_brackets(int(x_dev.numel()), q.ravel())
+    values = rt.order_stats(x_dev, np.concatenate([lo, hi]))
+    return _lerp_quantiles(values[:lo.size], values[lo.size:], gamma).reshape(q.shape)
+
+
+def sample_indices(size: int, sample: int):
+    """positions of the pixels `_fit_pixels` draws from an image of `size` pixels: np.random.choice on the GLOBAL NumPy RNG picks
+    values through a permutation of the positions, so drawing the positions themselves consumes the RNG identically and names the
+    same pixels"""
+    n = int(np.round(size / sample))
+    return np.random.choice(size, size=n, replace=False)
+
+
+def normalize_device(x_dev, alpha=900, beta=1, num_iters=100, sample=1, method='gmm'):
+    """`normalize` of a device tensor: (normalised float32 tensor on the device, the same metadata dict)"""
+    from . import runtime as rt
+    if method == 'affine':
+        # numpy's float32 pairwise mean / std are not what a device reduction gives bit for bit: the statistics stay numpy's
+        x = x_dev.cpu().numpy()
+        meta = {'mu': float(x.mean()), 'std': float(x.std()), 'pi': 1}
+        return rt.normalize(x_dev, meta['mu'], meta['std']), meta
+    size = int(x_dev.numel())
+    pixels, weight = x_dev.reshape(-1), 1
+    if sample > 1:
+        idx = sample_indices(size, sample)
+        pixels, weight = rt.gather(x_dev, idx), size / len(idx)
+    pis = np.array(INIT_PIS, dtype=np.float64)
+    splits = quantiles_device(pixels, 1 - pis)
+    mus, stds, pis_fit, logps, _ = rt.gmm_fit_fused(pixels, pis, splits, alpha=alpha, beta=beta, scale=weight,
+                                                    num_iters=num_iters, tol=1e-3)
+    i = int(np.argmax(logps))
+    meta = dict(zip(('mu', 'std', 'pi', 'logp') + _FIT_ARRAYS, (mus[i], stds[i], pis_fit[i], logps[i], mus, stds, pis_fit, logps)))
+    meta.update(alpha=alpha, beta=beta, sample=sample)
+    return rt.normalize_f64(x_dev, meta['mu'], meta['std']), meta
+
+
+def _normalize_stream(paths: List[str], dest: str, scale: int, fit_args: dict, metadata: bool, formats: List[str],
+                      verbose: bool) -> None:
+    """the loop of `normalize_images` over this process's files (structure: denoise._denoise_stream_device)"""
+    import queue
+    import threading
+    from . import runtime as rt
+    from .extract import ImageFeed
+    from .utils.image import downsample_device, save_image
+    if not paths:
+        return
+    affine = fit_args['method'] == 'affine'
+    ctx = rt.get_context()
+    out_stage, out_bytes, DEPTH = None, 0, 2
+    free_slots: 'queue.Queue' = queue.Queue()
+    todo: 'queue.Queue' = queue.Queue()
+    failed: list = []
+
+    def writer():
+        while True:
+            item = todo.get()
+            if item is None:
+                return
+            stage, k, shape, path, header, extended, meta, _device_result = item       # (the tensor lives until its copy is done)
+            try:
+                if not failed:
+                    stage.wait(k)                            # the D2H of this slot has landed
+                    pixels = stage.host_array(k, shape)
+                    if affine:
+                        # --affine keeps numpy's own statistics: the (down-sampled) image came down, the per-file expressions
+                        # run here, under the GPU's work on the next image
+                        pixels, meta = normalize(pixels, **fit_args)
+                    name = os.path.splitext(os.path.basename(path))[0]
+                    stem = os.path.join(dest, name)
+                    for fmt in formats:
+                        save_image(pixels, stem, f=fmt, header=header, extended_header=extended)
+                    if metadata:
+                        with open(stem + '.metadata.json', 'w') as fh:
+                            json.dump(_jsonable(meta), fh, indent=4)
+                    if verbose:
+                        print('# processed:', name, file=sys.stderr)
+            except BaseException as e:                       # surfaces in the main thread
+                failed.append(e)
+            finally:
+                free_slots.put((stage, k))
+
+    th = threading.Thread(target=writer, daemon=True)
+    th.start()
+    retired = []
+    feed = iter(ImageFeed(paths, ctx, headers=True))
+    try:
+        for path, x, header, extended in feed:
+            if scale > 1:
+                x = downsample_device(x, scale)
+                if header:
+                    header = header._replace(ny=x.shape[0], nx=x.shape[1])
+            if affine:
+                # (a copy when x is still the feed's own slot, which the feed re-uses once the next image is asked for)
+                y, meta = (x if scale > 1 else x.clone()), None
+            else:
+                y, meta = normalize_device(x, **fit_args)    # every RNG draw happens here, in path order
+            nbytes = y.numel() * 4
+            if out_stage is None or nbytes > out_bytes:
+                # (a larger image: a new ring; the old one is closed once the writer has drained it)
+                for _ in range(DEPTH if out_stage is not None else 0):
+                    free_slots.get()
+                if out_stage is not None:
+                    retired.append(out_stage)
+                out_bytes = (nbytes + (1 << 20) - 1) & ~((1 << 20) - 1)
+                out_stage = rt.Stage(ctx, out_bytes, DEPTH)
+                for k in range(DEPTH):
+                    free_slots.put((out_stage, k))
+            stage, k = free_slots.get()
+            if failed:
+                raise failed[0]
+            stage.download(k, y)
+            todo.put((stage, k, tuple(y.shape), path, header, extended, meta, y))
+    finally:
+        feed.close()                                         # joins the reader thread
+        todo.put(None)
+        th.join()
+        for st in retired + ([out_stage] if out_stage is not None else []):
+            st.close()
+    if failed:
+        raise failed[0]
+
+
 def normalize_images(paths: List[str], dest: str, num_workers: int, scale: int, affine: bool, niters: int, alpha: float,
                      beta: float, sample: int, metadata: bool, formats: List[str], use_cuda: bool = True,
                      verbose: bool = False):
-    """stats.py:334-352 (`num_workers` is accepted and unused: the fit runs on the GPU, one image at a time)"""
+    """stats.py:334-352 as a device-resident stream.  Rank r of a multi-process launch takes files r, r + world, ...; the ranks
+    write disjoint files and exchange nothing.  With sample > 1 each rank draws the sub-samples of ITS files from its own RNG, so
+    the fitted subsets depend on the number of ranks (sample = 1: the same files for any number).  `num_workers` is accepted and
+    unused: the parallelism is the reader / GPU / writer pipeline and the ranks."""
+    from . import parallel
+    rank, _, world = parallel.init_from_env()
     os.makedirs(dest, exist_ok=True)
-    worker = Normalize(dest, scale, affine, niters, alpha, beta, sample, metadata, formats)
-    for path in paths:
-        name = worker(path)
-        if verbose:
-            print('# processed:', name, file=sys.stderr)
+    mine = [paths[i] for i in parallel.shard_indices(len(paths), rank, world)]
+    fit_args = dict(alpha=alpha, beta=beta, num_iters=niters, sample=sample, method='affine' if affine else 'gmm')
+    _normalize_stream(mine, dest, scale, fit_args, metadata, formats, verbose)

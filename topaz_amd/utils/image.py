@@ -120,25 +120,33 @@ def _as_planes(t, channels, pixels):
     return t.reshape(channels, 1, pixels)
 
 
-def downsample(x, factor=1, shape=None):
-    """Downsample a 2-D array with a truncated DFT on the MI355X; numpy in, numpy out (dtype of x)."""
+def downsample_device(x_dev, factor=1, shape=None):
+    """`downsample` of a 2-D device tensor, the result left on the device (fp32 [m, n])"""
     import torch
     from .. import runtime as rt
-    x = np.asarray(x)
-    if x.ndim != 2:
+    if x_dev.dim() != 2:
         raise NotImplementedError('downsample: 2-D arrays only')
-    M, N = x.shape
+    M, N = x_dev.shape
     if shape is None:
         shape = (int(M / factor), int(N / factor))
     m, n = shape
     L, R = _downsample_operators(M, N, m, n)
-    xd = rt.as_device_f32(x, rt.get_context())
+    xd = rt.as_device_f32(x_dev, rt.get_context())
     U = rt.conv(_as_planes(xd, M, N), L.reshape(2 * m, M, 1, 1)).reshape(2 * m, N)           # [Re(U); Im(U)]
     Ut = rt.transpose(U)                                                                      # N x 2m
     # channels 0..N-1 read Re(U)^T (row stride 2m), channels N..2N-1 read Im(U)^T: feed both halves as one tensor
     Ucat = torch.cat([Ut[:, :m], Ut[:, m:]], 0).contiguous()                                  # 2N x m
     yt = rt.conv(_as_planes(Ucat, 2 * N, m), R.reshape(n, 2 * N, 1, 1)).reshape(n, m)
-    return rt.transpose(yt).cpu().numpy().astype(x.dtype)
+    return rt.transpose(yt)
+
+
+def downsample(x, factor=1, shape=None):
+    """Downsample a 2-D array with a truncated DFT on the MI355X; numpy in, numpy out (dtype of x)."""
+    import torch
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise NotImplementedError('downsample: 2-D arrays only')
+    return downsample_device(torch.from_numpy(np.ascontiguousarray(x)), factor, shape).cpu().numpy().astype(x.dtype)
 
 
 def downsample_file(path, scale, output, verbose=False):
