@@ -347,6 +347,27 @@ int tpz_ctx_set_raster(tpz_ctx* ctx, int on);
  * size (an 11 520 x 8 184 super-resolution frame: 146 GB).  Bit-identical to the whole-image pass. */
 int tpz_ctx_set_tiling(tpz_ctx* ctx, long long limit_px, int tile);
 int tpz_model_split_stats(tpz_model* m, int* eligible, long long* split_runs, long long* fp32_reruns);
+/* ---- precision check of a loaded model.  The 2xf16 path multiplies 22-bit operands; how far that leaves a given model from its
+ * own fp32 result depends on its weights, and a user-trained model is untested by construction.
+ * tpz_delta_stats: one streaming pass over two fp32 device arrays of n >= 1 elements (n = 0 is an error): max_abs_delta = max
+ *   |a[i] - b[i]| in fp32 with every non-finite difference (a NaN either side, inf - inf) counted as +inf, argmax = the smallest
+ *   flat index that attains it, max_abs_ref = max |b[i]| (NaN: +inf), sum_sq = the fp64 sum of (a[i] - b[i])^2.  Deterministic
+ *   (fixed reduction order, a grid chosen from n alone).  Synchronises.
+ * tpz_model_calibrate: one image d_in [D][H][W] (D = 1 in 2-D) through the model twice -- on the 2xf16 path exactly as
+ *   tpz_model_forward would run it (range scaling included), then on the fp32 kernels as under tpz_ctx_set_exact -- and
+ *   tpz_delta_stats of (2xf16 output, fp32 output) in d, rms_delta = sqrt(sum_sq / n).  eligible = 0 (and zeros) for a model
+ *   without a 2xf16 path; overflow = 1 (and no comparison) when the image left the f16 range, which the runtime re-runs in fp32
+ *   anyway.  With bar > 0, a max_abs_delta above it (or not finite) sets the model's exact flag and tripped = 1; bar <= 0 only
+ *   measures.  The counters of tpz_model_split_stats, the context's exact flag and its workspace are left as they were.  Never
+ *   called implicitly.
+ * tpz_model_set_exact: the per-model twin of tpz_ctx_set_exact -- the model is never tried on the 2xf16 path (scoring and
+ *   denoising alike; neither counter of tpz_model_split_stats moves); other models of the context are unaffected. */
+typedef struct tpz_delta { float max_abs_delta, max_abs_ref; long long argmax; double sum_sq; } tpz_delta;
+typedef struct tpz_calibration { int eligible, overflow, tripped; tpz_delta d; double rms_delta; } tpz_calibration;
+int tpz_delta_stats(tpz_ctx* ctx, const float* d_a, const float* d_b, size_t n, tpz_delta* out);
+int tpz_model_calibrate(tpz_model* m, const float* d_in, int D, int H, int W, float bar, tpz_calibration* out);
+int tpz_model_set_exact(tpz_model* m, int on);
+int tpz_model_get_exact(tpz_model* m, int* on);
 /* Coverage of the 2xf16 path: convolution layers of the model, how many of them have a 2xf16 kernel, and the others as text
  * ("#layer KxK dD cin->cout, ...").  `eligible` above is true as soon as ONE layer has: the rest of a mixed program runs on its
  * fp32 kernels (correct, converted either side, several times slower) -- topaz_amd warns once per model when that happens. */

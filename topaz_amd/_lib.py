@@ -33,6 +33,16 @@ class TpzLayer(C.Structure):
     ]
 
 
+class TpzDelta(C.Structure):
+    """struct tpz_delta of include/topaz_hip.h"""
+    _fields_ = [('max_abs_delta', C.c_float), ('max_abs_ref', C.c_float), ('argmax', C.c_longlong), ('sum_sq', C.c_double)]
+
+
+class TpzCalibration(C.Structure):
+    """struct tpz_calibration of include/topaz_hip.h"""
+    _fields_ = [('eligible', C.c_int), ('overflow', C.c_int), ('tripped', C.c_int), ('d', TpzDelta), ('rms_delta', C.c_double)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     'tpz_version': (C.c_char_p, []),
@@ -100,6 +110,10 @@ _SIGNATURES = {
     'tpz_ctx_set_rw': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_persist': (C.c_int, [_P, C.c_int, C.c_int]),
     'tpz_model_split_stats': (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    'tpz_delta_stats': (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(TpzDelta)]),
+    'tpz_model_calibrate': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(TpzCalibration)]),
+    'tpz_model_set_exact': (C.c_int, [_P, C.c_int]),
+    'tpz_model_get_exact': (C.c_int, [_P, C.POINTER(C.c_int)]),
     'tpz_model_split_layers': (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     'tpz_conv_split_2d': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_float, _P, C.c_int, _P, _P, _P, C.c_float, _P, C.POINTER(C.c_int)]),

@@ -15,6 +15,10 @@ Flag = Tuple[Sequence[str], Dict[str, Any]]
 
 _GPUS: Flag = (('--gpus',), dict(type=int, default=0, help='start this many rank processes, one per MI355X, and shard the '
                                    'inputs over them (0: a single process, or all GPUs with -d -2)'))
+_PRECISION: Flag = (('--precision-check',), dict(choices=['auto', 'always', 'never'], default='auto',
+                                                help='measure the 2xf16 path of each loaded model against its fp32 result on one seeded '
+                                                     'tile and run a model above 1e-4 on the fp32 kernels: auto checks model files '
+                                                     '(user-trained), always the pretrained aliases too, never nothing'))
 _THREADS: Flag = (('-j', '--num-threads'), dict(type=int, default=0, help='host threads for torch (0: library default, <0: all cores)'))
 
 EXTRACT: List[Flag] = [
@@ -42,6 +46,7 @@ EXTRACT: List[Flag] = [
     (('--dims',), dict(type=int, default=2, choices=[2, 3], help='2: micrographs, 3: tomograms')),
     (('-v', '--verbose'), dict(action='store_true', help='progress on stderr')),
     _GPUS,
+    _PRECISION,
 ]
 
 _TRAINING_ONLY = 'training option (not supported on this path)'
@@ -81,6 +86,7 @@ DENOISE: List[Flag] = [
     (('--num-workers',), dict(type=int, default=16, help=_TRAINING_ONLY)),
     _THREADS,
     _GPUS,
+    _PRECISION,
 ]
 
 DENOISE3D: List[Flag] = [
@@ -110,6 +116,7 @@ DENOISE3D: List[Flag] = [
     (('-p', '--patch-padding'), dict(type=int, default=48, help='halo around each tile')),
     (('-d', '--device'), dict(type=int, default=-2, help='-2: every visible MI355X (one rank process each; LOCAL_RANK when already under a launcher); >=0: that GPU; -1 is an error')),
     _GPUS,
+    _PRECISION,
 ]
 
 SEGMENT: List[Flag] = [
@@ -121,6 +128,7 @@ SEGMENT: List[Flag] = [
     (('-p', '--patch-size'), dict(type=int, default=None, help='score in tiles of twice this size (default: whole image)')),
     (('-v', '--verbose'), dict(action='store_true', help='progress on stdout')),
     _GPUS,
+    _PRECISION,
 ]
 
 DOWNSAMPLE: List[Flag] = [

@@ -6,6 +6,7 @@ import sys
 from .. import denoise as dn
 from ..cuda import set_device
 from ..denoise import Denoise, denoise_stack, denoise_stream
+from ..precision import check_loaded_model
 
 name = 'denoise'
 help = 'denoise micrographs with pretrained or user-supplied networks'
@@ -32,6 +33,7 @@ def main(args):
               file=sys.stderr)
         if arg != 'none':
             models.append(Denoise(arg, use_cuda))
+            check_loaded_model(models[-1].model, getattr(args, 'precision_check', 'auto'), arg, verbose=True)
     normalize = True if args.format_ in ['png', 'jpg'] else args.normalize
     gaus = dn.GaussianDenoise(args.gaussian, use_cuda=use_cuda) if args.gaussian > 0 else None
     inv_gaus = dn.InvGaussianFilter(args.inv_gaussian, use_cuda=use_cuda) if args.inv_gaussian > 0 else None

@@ -4,6 +4,7 @@ torchrun) and the volumes are sharded over the ranks."""
 import sys
 
 from ..denoise import Denoise3D, denoise_tomogram_stream
+from ..precision import check_loaded_model
 
 name = 'denoise3d'
 help = 'denoise tomograms tile by tile with a 3-D U-Net'
@@ -34,6 +35,7 @@ def main(args):
     print('# Warning: no denoising model will be used' if args.model == 'none' else '# Loading model:' + str(args.model),
           file=sys.stderr)
     denoiser = Denoise3D(args.model, True, dims=3)
+    check_loaded_model(denoiser.model, getattr(args, 'precision_check', 'auto'), args.model, verbose=True)
     total = len(args.volumes)
     if total < 1:
         return

@@ -18,7 +18,8 @@ def main(args):
     extract_particles(args.paths, args.model, args.device, args.batch_size, args.threshold, args.radius, args.num_workers,
                       args.targets, args.min_radius, args.max_radius, args.step_radius, args.assignment_radius,
                       args.patch_size, args.only_validate, args.output, args.per_micrograph, args.suffix, args.format,
-                      args.up_scale, args.down_scale, dims=args.dims, verbose=args.verbose)
+                      args.up_scale, args.down_scale, dims=args.dims, verbose=args.verbose,
+                      precision_check=getattr(args, 'precision_check', 'auto'))
 
 
 if __name__ == '__main__':

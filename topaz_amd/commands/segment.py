@@ -62,6 +62,8 @@ def main(args):
     model.eval()
     model.fill()
     model.cuda(args.device)
+    from ..precision import check_loaded_model
+    check_loaded_model(model, getattr(args, 'precision_check', 'auto'), args.model, args.verbose)
     if (args.patch_size is not None) and (args.patch_size <= 0):
         raise ValueError('patch size must be positive')
     segment_images(model, args.paths, args.destdir, use_cuda, args.verbose, args.patch_size)

@@ -58,6 +58,19 @@ hipError_t launch_unscale(float* y, size_t n, const float* rng, float add, hipSt
 hipError_t launch_extract_tile3d(const float* tomo, int D, int H, int W, int i0, int j0, int k0, int d,
                                  const float* d_g, float* tile, hipStream_t s);
 
+// delta_stats: max |a - b| (non-finite differences count as +inf) with the first index that attains it, max |b| (NaN: +inf) and
+// the fp64 sum of (a - b)^2 over n >= 1 elements, into *out on the device (the layout of tpz_delta, topaz_hip.h).  16-byte loads
+// when both pointers are 16-byte aligned, dword loads otherwise.  delta_stats_grid(n) workgroups -- a function of n alone -- leave
+// one partial each in `scratch` (DELTA_SCRATCH_BYTES) and one more workgroup folds them in order: two runs are bit-identical.
+struct DeltaStats {
+    float max_abs_delta, max_abs_ref;
+    long long argmax;
+    double sum_sq;
+};
+enum { DELTA_MAX_BLOCKS = 512, DELTA_SCRATCH_BYTES = 24 * DELTA_MAX_BLOCKS };
+int delta_stats_grid(size_t n);
+hipError_t launch_delta_stats(const float* a, const float* b, size_t n, void* scratch, DeltaStats* out, hipStream_t s);
+
 hipError_t nms_mark(const float* score, size_t n, float thr, uint8_t* status, uint32_t* cand, unsigned int* counters,
                     hipStream_t s);
 hipError_t nms2d_sweep(const float* score, int H, int W, const int* near_cells, int n_near, const int* cells, int ncells,

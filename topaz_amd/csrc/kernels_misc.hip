@@ -1028,4 +1028,120 @@ hipError_t launch_extract_tile3d(const float* tomo, int D, int H, int W, int i0,
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// delta_stats: how far two fp32 arrays are apart, in one streaming pass (the precision check of a loaded model compares its
+// 2xf16 output a with its fp32 output b: rt_forward.hip tpz_model_calibrate).
+//   max_d   max |a[i] - b[i]| in fp32, a non-finite difference (NaN either side, inf - inf) counting as +inf
+//   arg     the smallest flat index that attains it
+//   max_r   max |b[i]|, NaN counting as +inf
+//   ss      sum of (double)(a[i] - b[i])^2
+// Stage 1 leaves one partial per workgroup (lanes by __shfl_down, the four waves through the LDS), stage 2 -- one workgroup --
+// folds the partials in a fixed order: no atomics, the figures depend on (n, grid) only and the grid on n only.
+// ------------------------------------------------------------------------------------------
+struct DeltaAcc {
+    float d = -1.f, r = 0.f;              // (d = -1: below every |difference|, so that an all-equal pair still reports an index)
+    long long i = 0x7fffffffffffffffLL;
+    double ss = 0.0;
+    __device__ __forceinline__ void take(float x, float y, long long at) {
+        const float diff = x - y;
+        float ad = fabsf(diff), ar = fabsf(y);
+        if (!(ad <= 3.402823466e38f)) ad = __builtin_inff();
+        if (!(ar <= 3.402823466e38f)) ar = __builtin_inff();
+        if (ad > d || (ad == d && at < i)) { d = ad; i = at; }
+        r = fmaxf(r, ar);
+        ss += (double)diff * (double)diff;
+    }
+    // fold another accumulator in: the larger difference wins, the smaller index on a tie
+    __device__ __forceinline__ void fold(float od, long long oi, float orf, double oss) {
+        if (od > d || (od == d && oi < i)) { d = od; i = oi; }
+        r = fmaxf(r, orf);
+        ss += oss;
+    }
+};
+
+// the 256 accumulators of a workgroup -> thread 0's
+__device__ __forceinline__ void delta_block_reduce(DeltaAcc& acc) {
+    __shared__ float s_d[4], s_r[4];
+    __shared__ long long s_i[4];
+    __shared__ double s_ss[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_down(acc.d, o, 64), orf = __shfl_down(acc.r, o, 64);
+        const long long oi = __shfl_down(acc.i, o, 64);
+        const double oss = __shfl_down(acc.ss, o, 64);
+        acc.fold(od, oi, orf, oss);
+    }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_d[wv] = acc.d; s_r[wv] = acc.r; s_i[wv] = acc.i; s_ss[wv] = acc.ss; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) acc.fold(s_d[w], s_i[w], s_r[w], s_ss[w]);
+}
+
+// partials of all workgroups, one array per figure: [DELTA_MAX_BLOCKS] each
+struct DeltaPartials {
+    float* d;
+    float* r;
+    long long* i;
+    double* ss;
+};
+static inline DeltaPartials delta_partials(void* scratch) {
+    char* p = (char*)scratch;
+    return {(float*)(p + 8 * DELTA_MAX_BLOCKS), (float*)(p + 12 * DELTA_MAX_BLOCKS), (long long*)p,
+            (double*)(p + 16 * DELTA_MAX_BLOCKS)};
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(256) void delta_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
+                                                            DeltaPartials part) {
+    DeltaAcc acc;
+    const size_t t0 = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    if (VEC4) {
+        // both pointers 16-byte aligned: 16-byte loads over the whole float4s, the last n % 4 elements by the first threads
+        const size_t n4 = n >> 2;
+        const float4* a4 = (const float4*)a;
+        const float4* b4 = (const float4*)b;
+        for (size_t v = t0; v < n4; v += stride) {
+            const float4 x = a4[v], y = b4[v];
+            const long long at = (long long)(v << 2);
+            acc.take(x.x, y.x, at);
+            acc.take(x.y, y.y, at + 1);
+            acc.take(x.z, y.z, at + 2);
+            acc.take(x.w, y.w, at + 3);
+        }
+        const size_t tail = (n4 << 2) + t0;
+        if (tail < n) acc.take(a[tail], b[tail], (long long)tail);
+    } else {
+        for (size_t i = t0; i < n; i += stride) acc.take(a[i], b[i], (long long)i);
+    }
+    delta_block_reduce(acc);
+    if (threadIdx.x == 0) {
+        part.d[blockIdx.x] = acc.d; part.r[blockIdx.x] = acc.r; part.i[blockIdx.x] = acc.i; part.ss[blockIdx.x] = acc.ss;
+    }
+}
+
+__global__ __launch_bounds__(256) void delta_final_kernel(DeltaPartials part, int nblocks, DeltaStats* __restrict__ out) {
+    DeltaAcc acc;
+    for (int k = threadIdx.x; k < nblocks; k += 256) acc.fold(part.d[k], part.i[k], part.r[k], part.ss[k]);
+    delta_block_reduce(acc);
+    if (threadIdx.x == 0) { out->max_abs_delta = acc.d; out->max_abs_ref = acc.r; out->argmax = acc.i; out->sum_sq = acc.ss; }
+}
+
+int delta_stats_grid(size_t n) {
+    const size_t blocks = (n + 256 * 16 - 1) / (256 * 16);
+    return (int)std::min<size_t>(std::max<size_t>(blocks, 1), DELTA_MAX_BLOCKS);
+}
+
+hipError_t launch_delta_stats(const float* a, const float* b, size_t n, void* scratch, DeltaStats* out, hipStream_t s) {
+    if (n == 0) return hipErrorInvalidValue;
+    const int blocks = delta_stats_grid(n);
+    const DeltaPartials part = delta_partials(scratch);
+    if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0)
+        hipLaunchKernelGGL(delta_partial_kernel<true>, dim3(blocks), dim3(256), 0, s, a, b, n, part);
+    else
+        hipLaunchKernelGGL(delta_partial_kernel<false>, dim3(blocks), dim3(256), 0, s, a, b, n, part);
+    hipLaunchKernelGGL(delta_final_kernel, dim3(1), dim3(256), 0, s, part, blocks, out);
+    return hipGetLastError();
+}
+
 }  // namespace tpz

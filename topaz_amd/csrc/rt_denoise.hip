@@ -234,7 +234,7 @@ int tpz_denoise_2d(tpz_model* m, const float* d_in, int H, int W, int patch, int
     int Do, Ho, Wo;
     tpz_model_out_shape(m, 1, 8 * 64, 8 * 64, &Do, &Ho, &Wo);
     if (Ho != 8 * 64 || Wo != 8 * 64) return fail(ctx, "tpz_denoise_2d: the model does not preserve the image size");
-    if (m->split_ok && !ctx->exact) {
+    if (m->split_ok && !ctx->exact && !m->exact) {
         // 2xf16 path for the whole micrograph; any activation beyond the f16 range re-runs it on the fp32 kernels
         unsigned overflow = 0;
         HIPCHK(ctx, flag_clear(ctx));
@@ -253,7 +253,7 @@ int tpz_denoise_3d_shard(tpz_model* m, const float* d_in, int D, int H, int W, i
     if (patch < 1 && n_shards > 1) return fail(m->ctx, "tpz_denoise_3d_shard: an untiled volume cannot be sharded");
     tpz_ctx* ctx = m->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (m->split_ok && !ctx->exact) {
+    if (m->split_ok && !ctx->exact && !m->exact) {
         // 2xf16 path for the whole tomogram; any activation beyond the f16 range re-runs it on the fp32 kernels
         unsigned overflow = 0;
         HIPCHK(ctx, flag_clear(ctx));

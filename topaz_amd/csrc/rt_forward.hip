@@ -86,6 +86,71 @@ int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, i
     return 0;
 }
 
+// Which kernels an image takes through forward_image.
+enum PassMode {
+    PASS_DEFAULT,      // tpz_model_forward: the 2xf16 path where the model, the context and the volume allow it, re-run on the fp32
+                       // kernels when an activation left the f16 range; counts the image in n_split / n_fallback
+    PASS_SPLIT,        // the 2xf16 pass alone, as PASS_DEFAULT runs it (the caller has checked that the model has one): *overflow
+                       // reports the f16 range flag, nothing is re-run or counted
+    PASS_FP32,         // the fp32 kernels alone: what PASS_DEFAULT runs under tpz_ctx_set_exact
+};
+
+bool split_path_open(const tpz_model* m, int D, int H, int W) { return m->split_ok && split_volume_fits(m, D, H, W); }
+
+// One image x [D][H][W] through the program into out_b [Co][Do][Ho][Wo].
+int forward_image(tpz_model* m, float* x, int D, int H, int W, float* out_b, int Co, int Do, int Ho, int Wo, PassMode mode,
+                  unsigned* overflow_out = nullptr) {
+    tpz_ctx* ctx = m->ctx;
+    bool done = false;
+    if (mode == PASS_SPLIT || (mode == PASS_DEFAULT && !ctx->exact && !m->exact && split_path_open(m, D, H, W))) {
+        // 2xf16 path; an activation beyond the f16 range (flag) sends this image to the fp32 kernels instead
+        HIPCHK(ctx, flag_clear(ctx));
+        float* x_b = x;
+        // RANGE SCALING (scoring networks = programs ending in the linear head): `topaz extract` does not normalise its
+        // input (extract.py:234-249), and a raw-count micrograph would leave the f16 range in the stem.  The network is
+        // positively homogeneous in (input, biases): it runs on x * 2^-s with its biases scaled alike and the logits are
+        // multiplied back -- exact, powers of two; s follows the BULK of the image (its 99.9 % quantile of |x| -> ~8; s = 0 for
+        // a normalised image), so outliers cannot starve the rest of precision (kernels_misc.hip launch_range_fit).
+        const bool scaled = ctx->range_scaling && m->layers.back().L.op == TPZ_OP_CONV && m->layers.back().L.head &&
+                            m->d_bias_scaled != nullptr;
+        float *xs = nullptr, *rng = nullptr;
+        if (scaled) {
+            const size_t n_in = (size_t)D * H * W;
+            rng = next_nrm(ctx);
+            xs = (float*)pool_alloc(ctx, n_in * sizeof(float));
+            if (!xs) return fail(ctx, "out of device memory");
+            hipError_t e = enqueue(ctx, [=](hipStream_t st) {
+                return launch_range_fit(x_b, n_in, ctx->d_absmax, rng, m->d_bias_arena, m->d_bias_scaled, m->n_bias_arena, st);
+            });
+            if (e == hipSuccess) e = enqueue(ctx, [=](hipStream_t st) { return launch_affine_dev(x_b, D, H, W, (long long)H * W, W, rng, xs, st); });
+            if (e != hipSuccess) { pool_release(ctx, xs); return fail(ctx, "range scaling failed: %s", hipGetErrorString(e)); }
+            x_b = xs;
+            ctx->bias_shift = m->d_bias_scaled - m->d_bias_arena;
+            ctx->scaled_pass = true;
+        }
+        const int rc = run_image(m, x_b, D, H, W, out_b, Co, Do, Ho, Wo, true);
+        ctx->bias_shift = 0;
+        ctx->scaled_pass = false;
+        if (xs) pool_release(ctx, xs);
+        if (rc) return 1;
+        if (scaled) {
+            const size_t n_out = (size_t)Co * Do * Ho * Wo;
+            const float hb = m->layers.back().head_b;
+            HIPCHK(ctx, enqueue(ctx, [=](hipStream_t st) { return launch_unscale(out_b, n_out, rng, hb, st); }));
+        }
+        unsigned overflow = 0;
+        HIPCHK(ctx, flag_read(ctx, &overflow));
+        if (mode == PASS_SPLIT) {
+            if (overflow_out) *overflow_out = overflow;
+            return 0;
+        }
+        done = (overflow == 0);
+        if (done) ++m->n_split; else ++m->n_fallback;
+    }
+    if (!done && run_image(m, x, D, H, W, out_b, Co, Do, Ho, Wo, false)) return 1;
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace tpz::rt
@@ -102,52 +167,57 @@ int tpz_model_forward(tpz_model* m, const float* d_in, int n, int D, int H, int 
     if (Do < 1 || Ho < 1 || Wo < 1) return fail(ctx, "input %dx%dx%d too small for this model", D, H, W);
     int Co = 1;
     tpz_model_out_channels(m, &Co);
-    for (int b = 0; b < n; ++b) {
-        float* out_b = d_out + (size_t)b * Co * Do * Ho * Wo;
-        bool done = false;
-        if (m->split_ok && !ctx->exact && split_volume_fits(m, D, H, W)) {
-            // 2xf16 path; an activation beyond the f16 range (flag) sends this image to the fp32 kernels instead
-            HIPCHK(ctx, flag_clear(ctx));
-            float* x_b = const_cast<float*>(d_in) + (size_t)b * D * H * W;
-            // RANGE SCALING (scoring networks = programs ending in the linear head): `topaz extract` does not normalise its
-            // input (extract.py:234-249), and a raw-count micrograph would leave the f16 range in the stem.  The network is
-            // positively homogeneous in (input, biases): it runs on x * 2^-s with its biases scaled alike and the logits are
-            // multiplied back -- exact, powers of two; s follows the BULK of the image (its 99.9 % quantile of |x| -> ~8; s = 0 for
-            // a normalised image), so outliers cannot starve the rest of precision (kernels_misc.hip launch_range_fit).
-            const bool scaled = ctx->range_scaling && m->layers.back().L.op == TPZ_OP_CONV && m->layers.back().L.head &&
-                                m->d_bias_scaled != nullptr;
-            float *xs = nullptr, *rng = nullptr;
-            if (scaled) {
-                const size_t n_in = (size_t)D * H * W;
-                rng = next_nrm(ctx);
-                xs = (float*)pool_alloc(ctx, n_in * sizeof(float));
-                if (!xs) return fail(ctx, "out of device memory");
-                hipError_t e = enqueue(ctx, [=](hipStream_t st) {
-                    return launch_range_fit(x_b, n_in, ctx->d_absmax, rng, m->d_bias_arena, m->d_bias_scaled, m->n_bias_arena, st);
-                });
-                if (e == hipSuccess) e = enqueue(ctx, [=](hipStream_t st) { return launch_affine_dev(x_b, D, H, W, (long long)H * W, W, rng, xs, st); });
-                if (e != hipSuccess) { pool_release(ctx, xs); return fail(ctx, "range scaling failed: %s", hipGetErrorString(e)); }
-                x_b = xs;
-                ctx->bias_shift = m->d_bias_scaled - m->d_bias_arena;
-                ctx->scaled_pass = true;
-            }
-            const int rc = run_image(m, x_b, D, H, W, out_b, Co, Do, Ho, Wo, true);
-            ctx->bias_shift = 0;
-            ctx->scaled_pass = false;
-            if (xs) pool_release(ctx, xs);
-            if (rc) return 1;
-            if (scaled) {
-                const size_t n_out = (size_t)Co * Do * Ho * Wo;
-                const float hb = m->layers.back().head_b;
-                HIPCHK(ctx, enqueue(ctx, [=](hipStream_t st) { return launch_unscale(out_b, n_out, rng, hb, st); }));
-            }
-            unsigned overflow = 0;
-            HIPCHK(ctx, flag_read(ctx, &overflow));
-            done = (overflow == 0);
-            if (done) ++m->n_split; else ++m->n_fallback;
-        }
-        if (!done && run_image(m, const_cast<float*>(d_in) + (size_t)b * D * H * W, D, H, W, out_b, Co, Do, Ho, Wo, false)) return 1;
+    for (int b = 0; b < n; ++b)
+        if (forward_image(m, const_cast<float*>(d_in) + (size_t)b * D * H * W, D, H, W, d_out + (size_t)b * Co * Do * Ho * Wo, Co, Do,
+                          Ho, Wo, PASS_DEFAULT))
+            return 1;
+    return 0;
+}
+
+// The 2xf16 error of THIS model on THIS image against its own fp32 result (topaz_hip.h): the forced 2xf16 pass, the forced fp32
+// pass into a second buffer, delta_stats of the two.  Both passes go through forward_image, the function tpz_model_forward runs.
+int tpz_model_calibrate(tpz_model* m, const float* d_in, int D, int H, int W, float bar, tpz_calibration* out) {
+    if (!m || !d_in || !out) return fail(m ? m->ctx : nullptr, "tpz_model_calibrate: NULL argument");
+    tpz_ctx* ctx = m->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    memset(out, 0, sizeof *out);
+    int Do, Ho, Wo;
+    tpz_model_out_shape(m, D, H, W, &Do, &Ho, &Wo);
+    if (Do < 1 || Ho < 1 || Wo < 1) return fail(ctx, "tpz_model_calibrate: input %dx%dx%d too small for this model", D, H, W);
+    if (!split_path_open(m, D, H, W)) return 0;              // no 2xf16 path (for a volume of this size): nothing to compare
+    out->eligible = 1;
+    int Co = 1;
+    tpz_model_out_channels(m, &Co);
+    const size_t n_out = (size_t)Co * Do * Ho * Wo;
+    float* x = const_cast<float*>(d_in);
+    float* y_split = (float*)pool_alloc(ctx, n_out * sizeof(float));
+    float* y_exact = (float*)pool_alloc(ctx, n_out * sizeof(float));
+    int rc = (!y_split || !y_exact) ? fail(ctx, "out of device memory") : 0;
+    unsigned overflow = 0;
+    if (!rc) rc = forward_image(m, x, D, H, W, y_split, Co, Do, Ho, Wo, PASS_SPLIT, &overflow);
+    if (!rc && overflow) out->overflow = 1;                  // the runtime re-runs such an image in fp32 anyway
+    if (!rc && !overflow) rc = forward_image(m, x, D, H, W, y_exact, Co, Do, Ho, Wo, PASS_FP32);
+    if (!rc && !overflow) rc = delta_stats(ctx, y_split, y_exact, n_out, &out->d);
+    if (y_split) pool_release(ctx, y_split);
+    if (y_exact) pool_release(ctx, y_exact);
+    if (rc || overflow) return rc;
+    out->rms_delta = std::sqrt(out->d.sum_sq / (double)n_out);
+    if (bar > 0.f && !(out->d.max_abs_delta <= bar)) {      // (an infinite figure trips as well)
+        m->exact = true;
+        out->tripped = 1;
     }
+    return 0;
+}
+
+int tpz_model_set_exact(tpz_model* m, int on) {
+    if (!m) return fail(nullptr, "tpz_model_set_exact: model is NULL");
+    m->exact = on != 0;
+    return 0;
+}
+
+int tpz_model_get_exact(tpz_model* m, int* on) {
+    if (!m || !on) return fail(m ? m->ctx : nullptr, "tpz_model_get_exact: NULL argument");
+    *on = m->exact ? 1 : 0;
     return 0;
 }
 

@@ -11,9 +11,10 @@
 //                   DOES run on, in which tensor formats (ConvForm / ConvPlan below) --, the launch window (launch_window, with
 //                   its FLOP share and tile grid), launchers, per-layer drivers, the backward walk of the windows
 //                   (need_regions), run_program with its slot helpers (make_dst, source_view)
-//   rt_forward.hip  scoring drivers (range-scaled pass, internal tiling) and the single-op entry points
+//   rt_forward.hip  scoring drivers (range-scaled pass, internal tiling), the precision check of a loaded model
+//                   (tpz_model_calibrate) and the single-op entry points
 //   rt_denoise.hip  the patched 2-D and tiled 3-D denoising drivers (batched passes over the lanes)
-//   rt_stats.hip    mean / std, GMM fit, affine, normalise
+//   rt_stats.hip    mean / std, GMM fit, affine, normalise, delta_stats
 //   rt_preprocess.hip  the preprocess / normalize stream: radix-select order statistics, gather, the GMM fit with all
 //                   initialisations per pass, the float64 normalise (kernels there too)
 //   rt_stage.hip    the staging ring and the host-pointer entry points
@@ -339,6 +340,7 @@ struct tpz_model {
     bool split_ok = false;                // at least one layer has a 2xf16 kernel: the program runs in split mode
     bool widened = false;                 // the program was loaded with its widths zero-padded to multiples of 16 (widen_program)
     long long n_split = 0, n_fallback = 0;
+    bool exact = false;                   // never tried on the 2xf16 path (tpz_model_set_exact, a tripped tpz_model_calibrate)
 };
 
 namespace tpz::rt {
@@ -432,6 +434,8 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
                    bool pooled = false, const Slot* fold = nullptr);
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split = false,
                 const Rect* keep = nullptr);
+// rt_stats.hip: launch_delta_stats on the ctx stream, its result copied to the host (synchronises)
+int delta_stats(tpz_ctx* ctx, const float* d_a, const float* d_b, size_t n, tpz_delta* out);
 // ---- the scalar steps of the 2-component mixture fit (topaz/stats.py:87-203), shared by tpz_gmm_fit (rt_stats.hip: one
 // initialisation after the other) and tpz_gmm_fit_fused (rt_preprocess.hip: all of them per pass).  S / T are the seven sums of
 // gmm_pass_kernel, N the number of pixels.

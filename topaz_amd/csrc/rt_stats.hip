@@ -1,8 +1,35 @@
 // Statistics and elementwise entry points: mean / std, GMM fit (topaz normalize), affine, normalise.
+#include <cstddef>
 #include "rt_internal.h"
+
+namespace tpz::rt {
+
+static_assert(sizeof(tpz_delta) == sizeof(DeltaStats) && offsetof(tpz_delta, argmax) == offsetof(DeltaStats, argmax) &&
+                  offsetof(tpz_delta, sum_sq) == offsetof(DeltaStats, sum_sq),
+              "tpz_delta is what delta_final_kernel writes");
+static_assert(DELTA_SCRATCH_BYTES + sizeof(DeltaStats) <= 2 * PART_BLOCKS * sizeof(double), "delta_stats works in tpz_ctx::d_part");
+
+// the partials and, behind them, the result live in the reduction scratch of the ctx stream
+int delta_stats(tpz_ctx* ctx, const float* d_a, const float* d_b, size_t n, tpz_delta* out) {
+    DeltaStats* d_res = (DeltaStats*)((char*)ctx->d_part + DELTA_SCRATCH_BYTES);
+    HIPCHK(ctx, enqueue(ctx, [=](hipStream_t st) { return launch_delta_stats(d_a, d_b, n, ctx->d_part, d_res, st); }));
+    HIPCHK(ctx, hipMemcpyAsync(out, d_res, sizeof(tpz_delta), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+}  // namespace tpz::rt
 
 using namespace tpz;
 using namespace tpz::rt;
+
+int tpz_delta_stats(tpz_ctx* ctx, const float* d_a, const float* d_b, size_t n, tpz_delta* out) {
+    if (!ctx || !d_a || !d_b || !out) return fail(ctx, "tpz_delta_stats: NULL argument");
+    if (n == 0) return fail(ctx, "tpz_delta_stats: n = 0: nothing to compare");
+    if (n > ((size_t)1 << 40)) return fail(ctx, "tpz_delta_stats: n = %zu is above 2^40", n);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return delta_stats(ctx, d_a, d_b, n, out);
+}
 
 int tpz_mean_std(tpz_ctx* ctx, const float* d_x, size_t n, int unbiased, float* h_mean_std) {
     if (!ctx || !d_x || !h_mean_std || n == 0) return fail(ctx, "tpz_mean_std: bad arguments");

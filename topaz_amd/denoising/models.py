@@ -108,6 +108,14 @@ class DenoiseNet:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return self.device_model.forward(x)
 
+    def calibrate(self, x=None, bar: Optional[float] = None, seed: int = 0) -> dict:
+        """The 2xf16 error of the raw network (as net(x) runs it: no per-patch normalisation) against its own fp32 result on x
+        ([H, W] / [D, H, W]; None: RandomState(seed).randn, 256 x 256 or 48 x 48 x 48): DeviceModel.calibrate.  A figure above
+        `bar` (None: runtime.DEFAULT_BAR; <= 0: measure only) pins this model -- its patched denoising passes too -- to the fp32
+        kernels.  Never called implicitly."""
+        from ..precision import calibrate
+        return calibrate(self.device_model, x, bar, seed)
+
 
 def load_model(name, base_kernel_width: int = 11) -> DenoiseNet:
     """aliases -> packaged state_dicts; otherwise a path: a bare state_dict (3-D models,

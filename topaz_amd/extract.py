@@ -38,6 +38,7 @@ from .algorithms import match_coordinates, non_maximum_suppression, non_maximum_
 from .metrics import average_precision
 from .model.factory import load_model
 from .model.utils import predict_in_patches
+from .precision import check_loaded_model
 from .utils import files as file_utils
 from .utils.image import load_image
 from .utils.printing import report
@@ -344,7 +345,8 @@ class ImageFeed:
 class Scorer:
     """the filled scoring network on one MI355X"""
 
-    def __init__(self, model, device: int = 0):
+    def __init__(self, model, device: int = 0, precision_check: str = 'never', verbose: bool = False):
+        """precision_check: the `--precision-check` mode (precision.check_loaded_model: once, here, before the first image)"""
         if device is not None and device < 0:
             raise RuntimeError('topaz_amd has no CPU path: use -d >= 0 (an MI355X)')
         torch.cuda.set_device(device)
@@ -354,6 +356,7 @@ class Scorer:
         self.model.fill()
         self.model.cuda(device)
         self.ctx = self.model.device_model.ctx
+        self.precision = check_loaded_model(self.model, precision_check, model, verbose)
 
     def __call__(self, image: torch.Tensor, patch_size: int = 0):
         """[H, W] / [D, H, W] device tensor -> logits of the same shape (device tensor; float64 numpy when patched, like
@@ -367,15 +370,17 @@ class Scorer:
 
 
 def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int = 0, batch_size: int = 1,
-                 keep_on_device: bool = False) -> Iterator[Tuple[str, np.ndarray]]:
+                 keep_on_device: bool = False, precision_check: str = 'never',
+                 verbose: bool = False) -> Iterator[Tuple[str, np.ndarray]]:
     """generator of (path, score map).  `model` None / 'none': the inputs already are score maps and pass through.
-    keep_on_device=True yields device tensors (no PCIe round trip before the suppression)."""
+    keep_on_device=True yields device tensors (no PCIe round trip before the suppression).  precision_check / verbose: the
+    `--precision-check` mode of the loaded model (Scorer)."""
     paths = list(paths)
     if model is None or model == 'none':
         for path in paths:
             yield path, load_image(path, make_image=False, return_header=False)
         return
-    scorer = Scorer(model, device)
+    scorer = Scorer(model, device, precision_check, verbose)
     for path, image in ImageFeed(paths, scorer.ctx):
         scores = scorer(image, patch_size)
         if torch.is_tensor(scores) and not keep_on_device:
@@ -454,7 +459,7 @@ class PickSink:
 def extract_particles(paths: List[str], model, device: int, batch_size: int, threshold: float, radius: int,
                       num_workers: int, targets: str, min_radius: int, max_radius: int, step: int, match_radius: int,
                       patch_size, only_validate: bool, output: str, per_micrograph: bool, suffix: str, out_format: str,
-                      up_scale: float, down_scale: float, dims=2, verbose: bool = False):
+                      up_scale: float, down_scale: float, dims=2, verbose: bool = False, precision_check: str = 'never'):
     report('Beginning extraction')
     rank, local_rank, world = parallel.init_from_env()
     if world > 1:
@@ -470,7 +475,7 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
         paths = list(stream_inputs(sys.stdin))
     mine = parallel.shard_indices(len(paths), rank, world)
     maps = score_images(model, [paths[i] for i in mine], device=device, patch_size=patch_size, batch_size=batch_size,
-                        keep_on_device=True)
+                        keep_on_device=True, precision_check=precision_check, verbose=verbose)
     radius = -1 if radius is None else radius
 
     if targets is not None:

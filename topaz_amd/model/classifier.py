@@ -120,6 +120,15 @@ class LinearClassifier:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward(x)
 
+    def calibrate(self, x=None, bar: Optional[float] = None, seed: int = 0) -> dict:
+        """The 2xf16 error of the loaded, filled network against its own fp32 result on the image x ([H, W] / [D, H, W] or any
+        layout forward takes; None: RandomState(seed).randn, 256 x 256 or 48 x 48 x 48): DeviceModel.calibrate.  A figure above
+        `bar` (None: runtime.DEFAULT_BAR; <= 0: measure only) pins this model to the fp32 kernels.  Never called implicitly."""
+        if not self.filled:
+            raise NotImplementedError('calibrate needs the filled network (model.fill()): that is the network the MI355X path runs')
+        from ..precision import calibrate
+        return calibrate(self.device_model, x, bar, seed)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not self.filled:
             raise NotImplementedError('only the filled network (model.fill()) is implemented on the MI355X path; '

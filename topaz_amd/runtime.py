@@ -16,6 +16,11 @@ from ._lib import TpzLayer, check, load_library
 
 _contexts = {}
 
+# The bar of the precision check (DeviceModel.calibrate, `--precision-check`): the project's parity contract -- scores and
+# denoised pixels within 1e-4 absolute of the reference -- applied to the distance between a model's 2xf16 and fp32 results.
+# This is the one place it lives; it is read when a check runs.
+DEFAULT_BAR = 1e-4
+
 
 class Context:
     """tpz_ctx for one device.  Use get_context(device) rather than constructing directly."""
@@ -96,10 +101,26 @@ class Context:
         `workgroups` workgroups (0: one per grid slot)"""
         check(self.lib.tpz_ctx_set_persist(self.handle, int(mode), int(workgroups)), self.handle)
 
+    def delta_stats(self, a: torch.Tensor, b: torch.Tensor) -> dict:
+        """tpz_delta_stats of two fp32 device tensors of the same size: max |a - b| (a non-finite difference counts as inf), the
+        first flat index that attains it, max |b| and the float64 sum of (a - b)^2; deterministic"""
+        self.bind_current_stream()
+        a, b = as_device_f32(a, self).reshape(-1), as_device_f32(b, self).reshape(-1)
+        if a.numel() != b.numel():
+            raise ValueError(f'delta_stats: {a.numel()} against {b.numel()} elements')
+        out = _lib.TpzDelta()
+        check(self.lib.tpz_delta_stats(self.handle, _ptr(a), _ptr(b), a.numel(), C.byref(out)), self.handle)
+        return _delta_dict(out)
+
     def prof_get(self, cls: int) -> Tuple[float, int, float]:
         ms, n, fl = C.c_double(), C.c_longlong(), C.c_double()
         check(self.lib.tpz_prof_get(self.handle, cls, C.byref(ms), C.byref(n), C.byref(fl)), self.handle)
         return ms.value, n.value, fl.value
+
+
+def _delta_dict(d: '_lib.TpzDelta') -> dict:
+    return {'max_abs_delta': float(d.max_abs_delta), 'max_abs_ref': float(d.max_abs_ref), 'argmax': int(d.argmax),
+            'sum_sq': float(d.sum_sq)}
 
 
 def _prof_get_dominant(self):
@@ -430,10 +451,11 @@ class DeviceModel:
         check(self.ctx.lib.tpz_model_split_stats(self.handle, C.byref(e), C.byref(a), C.byref(b)), self.ctx.handle)
         return bool(e.value), a.value, b.value
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x: [N,1,(D,)H,W] (or without the channel axis) on the ctx device -> [N,1,(Do,)Ho,Wo]"""
-        self.ctx.bind_current_stream()
+    def _batch_input(self, x) -> Tuple[torch.Tensor, int, int, int, int, Tuple[int, int, int]]:
+        """x: [N,1,(D,)H,W] (or without the channel axis) -> (fp32 tensor on the ctx device, N, D, H, W, output size)"""
         nd = self.dims
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
         if x.dim() == nd + 1:
             x = x.unsqueeze(1)
         if x.dim() != nd + 2 or x.shape[1] != 1:
@@ -445,6 +467,40 @@ class DeviceModel:
         Do, Ho, Wo = self.out_shape(D, H, W)
         if min(Do, Ho, Wo) < 1:
             raise ValueError(f'input {tuple(x.shape)} is too small for this model')
+        return x, N, D, H, W, (Do, Ho, Wo)
+
+    def calibrate(self, x, bar: Optional[float] = None) -> dict:
+        """tpz_model_calibrate: the 2xf16 error of this model on the image x (any layout forward takes, N = 1) against its own
+        fp32 result.  Returns eligible / overflow / tripped (bools), max_abs_delta, max_abs_ref, argmax (flat index into the
+        output), sum_sq, rms_delta and the bar.  bar None: DEFAULT_BAR; a max_abs_delta above a bar > 0 pins this model to the
+        fp32 kernels (`exact`, tripped = True); bar <= 0 only measures.  No counter of split_stats() moves."""
+        self.ctx.bind_current_stream()
+        x, N, D, H, W, _ = self._batch_input(x)
+        if N != 1:
+            raise ValueError(f'calibrate takes one image, got a batch of {N}')
+        bar = DEFAULT_BAR if bar is None else float(bar)
+        out = _lib.TpzCalibration()
+        check(self.ctx.lib.tpz_model_calibrate(self.handle, _ptr(x), D, H, W, bar, C.byref(out)), self.ctx.handle)
+        r = _delta_dict(out.d)
+        r.update(eligible=bool(out.eligible), overflow=bool(out.overflow), tripped=bool(out.tripped),
+                 rms_delta=float(out.rms_delta), bar=bar)
+        return r
+
+    def set_exact(self, on: bool = True) -> None:
+        """pin this model to the fp32 MFMA kernels (tpz_model_set_exact), whatever its context runs otherwise"""
+        check(self.ctx.lib.tpz_model_set_exact(self.handle, 1 if on else 0), self.ctx.handle)
+
+    @property
+    def exact(self) -> bool:
+        on = C.c_int(0)
+        check(self.ctx.lib.tpz_model_get_exact(self.handle, C.byref(on)), self.ctx.handle)
+        return bool(on.value)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: [N,1,(D,)H,W] (or without the channel axis) on the ctx device -> [N,1,(Do,)Ho,Wo]"""
+        self.ctx.bind_current_stream()
+        nd = self.dims
+        x, N, D, H, W, (Do, Ho, Wo) = self._batch_input(x)
         co = C.c_int(1)
         check(self.ctx.lib.tpz_model_out_channels(self.handle, C.byref(co)), self.ctx.handle)
         shape = (N, co.value, Do, Ho, Wo) if nd == 3 else (N, co.value, Ho, Wo)
