@@ -263,9 +263,32 @@ int tpz_maxpool2(tpz_ctx* ctx, int dims, const float* d_in, int C, int D, int H,
  * back (values beyond the f16 range do not survive that: *overflow = 1, may be NULL).  Synchronises. */
 int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, int H, int W, int dil, int pad, int split,
              float* d_out, int* overflow);
-/* d_out[cols][rows] = d_in[rows][cols]; used by the truncated-DFT downsample (topaz/utils/image.py:38-61),
- * which runs as two GEMMs (tpz_conv with k = 1) around a transpose -- see topaz_amd/utils/image.py */
+/* d_out[cols][rows] = d_in[rows][cols] (the truncated-DFT downsample that once ran as two tpz_conv GEMMs around it is
+ * tpz_resample_* now) */
 int tpz_transpose_2d(tpz_ctx* ctx, const float* d_in, int rows, int cols, float* d_out);
+
+/* ---- truncated-DFT resampler ---------------------------------------------------------------- */
+/* replaces downsample(x, factor, shape) (topaz/utils/image.py:38-61: rfft2 -> keep the m x (n/2+1) low-frequency block -> scale ->
+ * irfft2), the first half of `topaz preprocess`.  That is a real-linear, separable map of the M x N image:
+ *     U = L x  (2m x N; L = [Re Lc; Im Lc], Lc the complex m x M row operator),   y = Re(U) R1 + Im(U) R2  (m x n),
+ * two fp32 GEMMs on the matrix cores (fp32 operands, fp32 accumulation: micrographs are detector counts).  A plan keeps the two
+ * operators of one shape on the device:
+ *   create  h_L [2m][M] and h_R [n][2N] (= [R1; R2] transposed) on the host, fp32, row-major (topaz_amd/utils/image.py builds
+ *           them in float64 with numpy's own FFT); packed and uploaded once.  1 <= m <= M, 1 <= n <= N.  Synchronous.
+ *   run     d_in [M][N] -> d_out [m][n], dense device arrays that must not overlap; two launches on the ctx stream, the
+ *           intermediate from the ctx workspace: no host packing, no operator upload, no synchronise.  Bit-identical run to run.
+ *   free    waits for the ctx stream (runs already enqueued still read the operators), then releases the plan.  A plan must be
+ *           freed before its ctx is destroyed.
+ * tpz_resample_2d_host: run on host arrays h_in [M][N] -> h_out [m][n] through the ctx's staging ring (synchronous).
+ * tpz_resample_upload_bytes: operator bytes this ctx has uploaded in all its tpz_resample_create calls so far -- a run on an
+ * existing plan leaves it unchanged. */
+typedef struct tpz_resample tpz_resample;
+int tpz_resample_create(tpz_ctx* ctx, int M, int N, int m, int n, const float* h_L, const float* h_R, tpz_resample** out);
+int tpz_resample_run(tpz_resample* plan, const float* d_in, float* d_out);
+void tpz_resample_free(tpz_resample* plan);
+int tpz_resample_shape(tpz_resample* plan, int* M, int* N, int* m, int* n);
+int tpz_resample_2d_host(tpz_resample* plan, const float* h_in, float* h_out);
+long long tpz_resample_upload_bytes(tpz_ctx* ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------- */
 /* ---- 2xf16 path.  Every convolution with a conv_split kernel -- the scoring networks (stem as a column kernel, dilated

@@ -98,6 +98,12 @@ _SIGNATURES = {
     'tpz_pool': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                            C.POINTER(C.c_int)]),
     'tpz_transpose_2d': (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    'tpz_resample_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(_P)]),
+    'tpz_resample_run': (C.c_int, [_P, _P, _P]),
+    'tpz_resample_free': (None, [_P]),
+    'tpz_resample_shape': (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'tpz_resample_2d_host': (C.c_int, [_P, _P, _P]),
+    'tpz_resample_upload_bytes': (C.c_longlong, [_P]),
     'tpz_ctx_set_exact': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_lanes': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_batch': (C.c_int, [_P, C.c_int]),

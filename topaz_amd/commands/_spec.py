@@ -47,6 +47,21 @@ EXTRACT: List[Flag] = [
     (('-v', '--verbose'), dict(action='store_true', help='progress on stderr')),
     _GPUS,
     _PRECISION,
+    (('--preprocess',), dict(type=int, default=0, metavar='S',
+                             help='pick from raw micrographs: put every input through what `topaz preprocess -s S` does -- Fourier '
+                                  'down-sampling by S (when S > 1), then normalisation -- in device memory before it is scored '
+                                  '(0: off; 1: normalise only).  Picks are in the frame of the scored, S times smaller image, '
+                                  'exactly as when `topaz preprocess` wrote it to a file first: -x S scales them back to the raw '
+                                  'frame.  Needs --dims 2 and a model')),
+    (('--preprocess-affine',), dict(action='store_true', help='--preprocess: plain (x - mean) / std instead of the mixture fit '
+                                                              '(`topaz preprocess --affine`)')),
+    (('--preprocess-sample',), dict(type=int, default=10, help='--preprocess: fit the mixture on every n-th pixel '
+                                                               '(`topaz preprocess --sample`)')),
+    (('--preprocess-niters',), dict(type=int, default=100, help='--preprocess: cap on the EM iterations of one fit (`--niters`)')),
+    (('--preprocess-alpha',), dict(type=float, default=900, help='--preprocess: alpha of the Beta prior on the mixing proportion '
+                                                                 '(`--alpha`)')),
+    (('--preprocess-beta',), dict(type=float, default=1, help='--preprocess: beta of the Beta prior on the mixing proportion '
+                                                              '(`--beta`)')),
 ]
 
 _TRAINING_ONLY = 'training option (not supported on this path)'

@@ -13,13 +13,23 @@ def add_arguments(parser=None):
 
 
 def main(args):
+    from ..extract import check_preprocess_args
     from ..torch import set_num_threads
+    scale = getattr(args, 'preprocess', 0)
+    if scale < 0:
+        raise ValueError(f'--preprocess {scale}: a reduction factor >= 1, or 0 for off')
+    check_preprocess_args(scale, args.model, args.dims)
+    preprocess = None
+    if scale:
+        from ..stats import DevicePreprocess
+        preprocess = DevicePreprocess(scale, args.preprocess_affine, args.preprocess_niters, args.preprocess_alpha,
+                                      args.preprocess_beta, args.preprocess_sample)
     set_num_threads(args.num_threads)
     extract_particles(args.paths, args.model, args.device, args.batch_size, args.threshold, args.radius, args.num_workers,
                       args.targets, args.min_radius, args.max_radius, args.step_radius, args.assignment_radius,
                       args.patch_size, args.only_validate, args.output, args.per_micrograph, args.suffix, args.format,
                       args.up_scale, args.down_scale, dims=args.dims, verbose=args.verbose,
-                      precision_check=getattr(args, 'precision_check', 'auto'))
+                      precision_check=getattr(args, 'precision_check', 'auto'), preprocess=preprocess)
 
 
 if __name__ == '__main__':

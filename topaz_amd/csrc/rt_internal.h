@@ -21,6 +21,7 @@
 //   rt_nms.hip      the NMS driver
 //   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
 //   rt_prefilter.hip  denoise pre-filters: fp64 low-pass GEMMs, tile covariances, the per-tile deconvolution filter (kernels there too)
+//   rt_resample.hip   the truncated-DFT resampler: plans with device-resident operators over the fp32-MFMA GEMM of resample_gemm.h
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -153,6 +154,7 @@ struct tpz_ctx {
     int rec_lane = 0;
     long long batch_mem = 0;                  // tpz_ctx_set_batch_memory: device bytes a batched pass may take (0: what is free)
     long long n_launches = 0;                 // kernel launches issued (tpz_prof_launches)
+    long long resample_upload_bytes = 0;      // operator bytes uploaded by tpz_resample_create (tpz_resample_upload_bytes)
     double* d_part = nullptr;     // reduction partials
     float* d_nrm = nullptr;       // ring of float[4] normalisation parameter blocks
     int nrm_next = 0;
@@ -434,6 +436,8 @@ int run_conv_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const Slot* 
                    bool pooled = false, const Slot* fold = nullptr);
 int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const float* d_nrm, bool split = false,
                 const Rect* keep = nullptr);
+// rt_resample.hip: the ctx a resampler plan belongs to (rt_stage.hip stages tpz_resample_2d_host through that ctx's ring)
+tpz_ctx* resample_ctx(tpz_resample* plan);
 // rt_stats.hip: launch_delta_stats on the ctx stream, its result copied to the host (synchronises)
 int delta_stats(tpz_ctx* ctx, const float* d_a, const float* d_b, size_t n, tpz_delta* out);
 // ---- the scalar steps of the 2-component mixture fit (topaz/stats.py:87-203), shared by tpz_gmm_fit (rt_stats.hip: one

@@ -146,6 +146,21 @@ int tpz_denoise_2d_host(tpz_model* m, const float* h_in, int H, int W, int patch
     memcpy(h_out, tpz_stage_host_ptr(st, 1), nb);
     return tpz_stage_release(st, 1);
 }
+int tpz_resample_2d_host(tpz_resample* plan, const float* h_in, float* h_out) {
+    tpz_ctx* ctx = resample_ctx(plan);
+    if (!plan || !h_in || !h_out) return fail(ctx, "tpz_resample_2d_host: bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int M, N, m, n;
+    tpz_resample_shape(plan, &M, &N, &m, &n);
+    const size_t nin = (size_t)M * N * sizeof(float), nout = (size_t)m * n * sizeof(float);
+    tpz_stage* st;
+    if (io_stage(ctx, nin, &st)) return 1;
+    if (tpz_stage_h2d(st, 0, h_in, nin) || tpz_stage_acquire(st, 0)) return 1;
+    if (tpz_resample_run(plan, (const float*)tpz_stage_device_ptr(st, 0), (float*)tpz_stage_device_ptr(st, 1))) return 1;
+    if (tpz_stage_release(st, 0) || tpz_stage_d2h(st, 1, tpz_stage_device_ptr(st, 1), nout) || tpz_stage_wait(st, 1)) return 1;
+    memcpy(h_out, tpz_stage_host_ptr(st, 1), nout);
+    return tpz_stage_release(st, 1);
+}
 int tpz_nms_2d_host(tpz_ctx* ctx, const float* h_score, int H, int W, int r, float threshold, int32_t* h_coords,
                     float* h_scores, int cap, int* h_n) {
     if (!ctx || !h_score || !h_coords || !h_scores || H < 1 || W < 1 || cap < 0) return fail(ctx, "tpz_nms_2d_host: bad arguments");

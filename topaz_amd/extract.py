@@ -371,21 +371,38 @@ class Scorer:
 
 def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int = 0, batch_size: int = 1,
                  keep_on_device: bool = False, precision_check: str = 'never',
-                 verbose: bool = False) -> Iterator[Tuple[str, np.ndarray]]:
+                 verbose: bool = False, preprocess=None) -> Iterator[Tuple[str, np.ndarray]]:
     """generator of (path, score map).  `model` None / 'none': the inputs already are score maps and pass through.
     keep_on_device=True yields device tensors (no PCIe round trip before the suppression).  precision_check / verbose: the
-    `--precision-check` mode of the loaded model (Scorer)."""
+    `--precision-check` mode of the loaded model (Scorer).  preprocess: a callable device tensor -> device tensor (e.g.
+    stats.DevicePreprocess) applied to every image the feed yields before it is scored -- here, in the consuming thread and in
+    path order, so whatever it draws from the NumPy RNG is drawn in the order `topaz preprocess` draws it."""
     paths = list(paths)
     if model is None or model == 'none':
+        if preprocess is not None:
+            raise ValueError('preprocess needs a model: score maps are not micrographs')
         for path in paths:
             yield path, load_image(path, make_image=False, return_header=False)
         return
     scorer = Scorer(model, device, precision_check, verbose)
     for path, image in ImageFeed(paths, scorer.ctx):
+        if preprocess is not None:
+            image = preprocess(image)
         scores = scorer(image, patch_size)
         if torch.is_tensor(scores) and not keep_on_device:
             scores = scores.cpu().numpy()
         yield path, scores
+
+
+def check_preprocess_args(preprocess, model, dims) -> None:
+    """`--preprocess` is the 2-D `topaz preprocess` in front of a scoring network: refused for tomograms and for inputs that
+    already are score maps.  Raises ValueError; touches neither the GPU nor a model file."""
+    if not preprocess:
+        return
+    if dims != 2:
+        raise ValueError('--preprocess works on micrographs (--dims 2): `topaz preprocess` has no 3-D form')
+    if model is None or model == 'none':
+        raise ValueError('--preprocess needs a model (-m): with -m none the inputs already are score maps')
 
 
 def stream_inputs(f) -> Iterator[str]:
@@ -459,7 +476,13 @@ class PickSink:
 def extract_particles(paths: List[str], model, device: int, batch_size: int, threshold: float, radius: int,
                       num_workers: int, targets: str, min_radius: int, max_radius: int, step: int, match_radius: int,
                       patch_size, only_validate: bool, output: str, per_micrograph: bool, suffix: str, out_format: str,
-                      up_scale: float, down_scale: float, dims=2, verbose: bool = False, precision_check: str = 'never'):
+                      up_scale: float, down_scale: float, dims=2, verbose: bool = False, precision_check: str = 'never',
+                      preprocess=None):
+    """preprocess: None, or a callable device tensor -> device tensor (stats.DevicePreprocess) every micrograph goes through
+    before it is scored (`--preprocess`).  Everything downstream -- patches, the radius search, the ranks, the outputs -- sees
+    the smaller, normalised image only: picks are in ITS frame, as they are when `topaz preprocess` wrote it to a file first;
+    up_scale / down_scale move them, as ever."""
+    check_preprocess_args(preprocess, model, dims)               # (before anything is loaded)
     report('Beginning extraction')
     rank, local_rank, world = parallel.init_from_env()
     if world > 1:
@@ -475,7 +498,7 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
         paths = list(stream_inputs(sys.stdin))
     mine = parallel.shard_indices(len(paths), rank, world)
     maps = score_images(model, [paths[i] for i in mine], device=device, patch_size=patch_size, batch_size=batch_size,
-                        keep_on_device=True, precision_check=precision_check, verbose=verbose)
+                        keep_on_device=True, precision_check=precision_check, verbose=verbose, preprocess=preprocess)
     radius = -1 if radius is None else radius
 
     if targets is not None:

@@ -35,8 +35,36 @@ def init_from_env(backend: Optional[str] = None) -> Tuple[int, int, int]:
             torch.cuda.set_device(local_rank)
             dist.init_process_group(backend, rank=rank, world_size=world, device_id=torch.device('cuda', local_rank))
         else:
-            dist.init_process_group(backend, rank=rank, world_size=world)
+            with _stdout_to_stderr():
+                dist.init_process_group(backend, rank=rank, world_size=world)
     return rank, local_rank, world
+
+
+class _stdout_to_stderr:
+    """File descriptor 1 points at stderr inside the block.  The gloo library announces every rank's connections on stdout
+    ("[Gloo] Rank r is connected to ...") while the process group is built, in several writes per line: the ranks of one job
+    share the launcher's stdout, their banners interleave there, and fragments of them ended up between the lines of a command
+    whose stdout is its result (`extract --targets`).  Diagnostics belong on stderr; stdout is back when the block ends."""
+
+    def __enter__(self):
+        self.saved = None
+        try:
+            sys.stdout.flush()
+            self.saved = os.dup(1)
+            os.dup2(2, 1)
+        except (OSError, ValueError):
+            if self.saved is not None:
+                os.close(self.saved)
+                self.saved = None
+        return self
+
+    def __exit__(self, *exc):
+        if self.saved is not None:
+            try:
+                os.dup2(self.saved, 1)
+            finally:
+                os.close(self.saved)
+        return False
 
 
 def rank_device(local_rank: int) -> int:

@@ -863,6 +863,70 @@ def nms(score: torch.Tensor, r: int, threshold: float, scale: float = 1.0, ctx: 
         return out[:n.value], coords[:n.value]
 
 
+class ResamplePlan:
+    """tpz_resample: the two operators of one truncated-DFT reduction (M, N) -> (m, n), packed and resident in HBM.  L [2m, M] and
+    R [n, 2N] are the float32 host operators of utils.image._downsample_operators; they are uploaded here, once.  run() only
+    enqueues on the ctx stream.  close() (or the last reference going away) waits for that stream and frees the operators."""
+
+    def __init__(self, L: np.ndarray, R: np.ndarray, ctx: Optional[Context] = None):
+        self.ctx = ctx or get_context()
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 2 or R.ndim != 2 or L.shape[0] % 2 or R.shape[1] % 2:
+            raise ValueError(f'resample operators [2m, M] and [n, 2N] expected, got {L.shape} and {R.shape}')
+        self.shape_in = (L.shape[1], R.shape[1] // 2)
+        self.shape_out = (L.shape[0] // 2, R.shape[0])
+        h = C.c_void_p()
+        check(self.ctx.lib.tpz_resample_create(self.ctx.handle, self.shape_in[0], self.shape_in[1], self.shape_out[0],
+                                               self.shape_out[1], L.ctypes.data_as(C.c_void_p), R.ctypes.data_as(C.c_void_p),
+                                               C.byref(h)), self.ctx.handle)
+        self.handle = h
+
+    def run(self, x: torch.Tensor) -> torch.Tensor:
+        """x: fp32 [M, N] on the ctx device -> fp32 [m, n] on the device.  A non-contiguous view (or another dtype / device) is
+        copied into a dense fp32 device tensor first (as_device_f32); the kernel only ever reads dense rows."""
+        if not self.handle:
+            raise _lib.TopazHipError('resample plan used after close()')
+        if tuple(x.shape) != self.shape_in:
+            raise ValueError(f'resample plan for {self.shape_in} images, got {tuple(x.shape)}')
+        self.ctx.bind_current_stream()
+        x = as_device_f32(x, self.ctx)
+        y = torch.empty(self.shape_out, dtype=torch.float32, device=x.device)
+        check(self.ctx.lib.tpz_resample_run(self.handle, _ptr(x), _ptr(y)), self.ctx.handle)
+        return y
+
+    def run_host(self, x: np.ndarray) -> np.ndarray:
+        """tpz_resample_2d_host: numpy image in, numpy image out (synchronous; staged inside the library)"""
+        if not self.handle:
+            raise _lib.TopazHipError('resample plan used after close()')
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.shape != self.shape_in:
+            raise ValueError(f'resample plan for {self.shape_in} images, got {x.shape}')
+        self.ctx.bind_current_stream()
+        y = np.empty(self.shape_out, dtype=np.float32)
+        check(self.ctx.lib.tpz_resample_2d_host(self.handle, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p)),
+              self.ctx.handle)
+        return y
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            self.ctx.lib.tpz_resample_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def resample_upload_bytes(ctx: Optional[Context] = None) -> int:
+    """operator bytes the context has uploaded for resample plans so far (tpz_resample_upload_bytes): grows when a plan is
+    created, never when one runs"""
+    ctx = ctx or get_context()
+    return int(ctx.lib.tpz_resample_upload_bytes(ctx.handle))
+
+
 def transpose(x: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     ctx = ctx or get_context()
     ctx.bind_current_stream()

@@ -206,6 +206,30 @@ def normalize_device(x_dev, alpha=900, beta=1, num_iters=100, sample=1, method='
     return rt.normalize_f64(x_dev, meta['mu'], meta['std']), meta
 
 
+class DevicePreprocess:
+    """What `topaz preprocess -s scale` does to one micrograph, on a device tensor: Fourier down-sampling by `scale` (when > 1), then
+    the mixture-fit (or `affine`) normalisation -- the two steps of `_normalize_stream` below, through the same functions, so the
+    result equals the file `topaz preprocess` writes bit for bit.  `topaz extract --preprocess` applies it to every image before
+    scoring.  With sample > 1 each call draws from the global NumPy RNG: call it in path order.  `last_meta` keeps the metadata
+    of the latest call (what --metadata would have written)."""
+
+    def __init__(self, scale=1, affine=False, niters=100, alpha=900, beta=1, sample=10):
+        self.scale = int(scale)
+        if self.scale < 1:
+            raise ValueError(f'preprocess scale must be >= 1, got {scale}')
+        self.fit_args = dict(alpha=alpha, beta=beta, num_iters=niters, sample=sample, method='affine' if affine else 'gmm')
+        self.last_meta = None
+
+    def __call__(self, x_dev):
+        from .utils.image import downsample_device
+        if x_dev.dim() != 2:
+            raise NotImplementedError('preprocess: 2-D micrographs only')
+        if self.scale > 1:
+            x_dev = downsample_device(x_dev, self.scale)
+        y, self.last_meta = normalize_device(x_dev, **self.fit_args)
+        return y
+
+
 def _normalize_stream(paths: List[str], dest: str, scale: int, fit_args: dict, metadata: bool, formats: List[str],
                       verbose: bool) -> None:
     """the loop of `normalize_images` over this process's files (structure: denoise._denoise_stream_device)"""

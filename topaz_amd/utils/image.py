@@ -91,7 +91,8 @@ def save_image(x, path, mi=-3, ma=3, f=None, verbose=False, header=None, extende
 # complex intermediate U = Lc x, two real column operators:  y = Re(U) R1 + Im(U) R2.  The operators are built
 # once per shape in float64 with numpy's own FFT applied to identity matrices (so every convention -- which
 # rows `F[-m//2:]` keeps for odd m, how irfft treats the Nyquist bin -- is inherited, not re-derived), and the
-# image goes through two GEMMs on the fp32 MFMA kernel (1x1 convolutions) and two transposes on the device.
+# image goes through two fp32-MFMA GEMMs on the device (csrc/rt_resample.hip): U = L x, then y = Re(U) R1 + Im(U) R2 as one
+# launch whose K loop walks both (U half, R half) pairs.
 _DS_CACHE = {}
 
 
@@ -112,17 +113,29 @@ def _downsample_operators(M, N, m, n):
     return _DS_CACHE[key]
 
 
-def _as_planes(t, channels, pixels):
-    """[channels][pixels] matrix as a [C][H][W] tensor for the 1x1-conv GEMM (any H*W = pixels works)"""
-    for w in (64, 32, 16):
-        if pixels % w == 0:
-            return t.reshape(channels, pixels // w, w)
-    return t.reshape(channels, 1, pixels)
+# The operators of a shape live on the device as a resample plan (runtime.ResamplePlan, tpz_resample_*): packed and uploaded when
+# the shape is first seen, after that a downsample is two launches and nothing else.  A few shapes are kept (a data set has one or
+# two frame sizes; a 4096^2 -> 1024^2 plan holds 64 MB); the oldest plan is closed -- its device memory freed, after the work
+# already enqueued on it -- when a new shape needs the room.
+_PLAN_CACHE = {}
+_PLAN_CACHE_MAX = 4
+
+
+def _resample_plan(ctx, M, N, m, n):
+    from .. import runtime as rt
+    key = (ctx.device, M, N, m, n)
+    plan = _PLAN_CACHE.pop(key, None)
+    if plan is None:
+        while len(_PLAN_CACHE) >= _PLAN_CACHE_MAX:
+            _PLAN_CACHE.pop(next(iter(_PLAN_CACHE))).close()
+        L, R = _downsample_operators(M, N, m, n)
+        plan = rt.ResamplePlan(L, R, ctx)
+    _PLAN_CACHE[key] = plan                                      # (re-inserted: the dict is in least-recently-used order)
+    return plan
 
 
 def downsample_device(x_dev, factor=1, shape=None):
     """`downsample` of a 2-D device tensor, the result left on the device (fp32 [m, n])"""
-    import torch
     from .. import runtime as rt
     if x_dev.dim() != 2:
         raise NotImplementedError('downsample: 2-D arrays only')
@@ -130,14 +143,7 @@ def downsample_device(x_dev, factor=1, shape=None):
     if shape is None:
         shape = (int(M / factor), int(N / factor))
     m, n = shape
-    L, R = _downsample_operators(M, N, m, n)
-    xd = rt.as_device_f32(x_dev, rt.get_context())
-    U = rt.conv(_as_planes(xd, M, N), L.reshape(2 * m, M, 1, 1)).reshape(2 * m, N)           # [Re(U); Im(U)]
-    Ut = rt.transpose(U)                                                                      # N x 2m
-    # channels 0..N-1 read Re(U)^T (row stride 2m), channels N..2N-1 read Im(U)^T: feed both halves as one tensor
-    Ucat = torch.cat([Ut[:, :m], Ut[:, m:]], 0).contiguous()                                  # 2N x m
-    yt = rt.conv(_as_planes(Ucat, 2 * N, m), R.reshape(n, 2 * N, 1, 1)).reshape(n, m)
-    return rt.transpose(yt)
+    return _resample_plan(rt.get_context(), M, N, m, n).run(x_dev)
 
 
 def downsample(x, factor=1, shape=None):
