@@ -1,6 +1,7 @@
 """Measure `topaz particle_stack` on one MI355X (the numbers behind profiles/particle_stack.txt and DESIGN.md section 8).
 
     python tools/bench_particle_stack.py [--mics 8] [--picks 2000] [--size 256] [--resize 128] [--cpu-runs 3] [--tmp /dev/shm]
+                                         [--fused | --fused-only] [--two-command-root DIR]
 
 Workload: `--mics` synthetic 4096^2 float32 micrographs (seeded Poisson(5000) counts) with `--picks` picks each (uniform over
 the image, boxes cut by the edges included), run once at --size and once at --size -> --resize.  Reports
@@ -10,6 +11,9 @@ the image, boxes cut by the edges included), run once at --size and once at --si
     tmpfs,
   - the same workload through a numpy restatement of the reference loop (topaz/utils/picks.py:132-163, the resize as the
     per-frame 2-D truncated DFT) on the same host: 1 warm-up and --cpu-runs timed runs, median and spread.
+With --fused / --fused-only also (or only) the leg behind profiles/extract_particle_stack.txt and DESIGN.md section 13:
+`extract --particle-stack` against `extract` followed by `particle_stack` on the same micrographs (fused_leg); with
+--two-command-root DIR the two commands run from the source tree DIR, e.g. a checkout of the parent commit with its built library.
 """
 from __future__ import annotations
 
@@ -102,6 +106,73 @@ def numpy_reference(picks, d, S, R):
                 f.write(stack.tobytes())
 
 
+# raw frames -> picks in the raw frame (--preprocess-sample 1: no RNG draw, every run writes the same table)
+EXTRACT = '-m resnet8_u32 -r 8 -t -100 -d 0 --preprocess 4 --preprocess-sample 1 -x 4'
+
+
+def _cli(argv, root=ROOT):
+    t0 = time.perf_counter()
+    subprocess.run([sys.executable, '-m', 'topaz_amd'] + argv, cwd=root, check=True, capture_output=True)
+    return time.perf_counter() - t0
+
+
+def _particle_kernels(ctx, n_mics):
+    rows = [r for r in ctx.prof_kernels() if r[0].startswith('particle_')]
+    return sum(r[1] for r in rows) / n_mics, sum(r[2] for r in rows)
+
+
+def fused_leg(d, S, R, n_mics, n_picks, extract_args, two_root=ROOT, runs=3):
+    """`extract --particle-stack` against `extract` followed by `particle_stack` on the same micrographs: CLI wall time per
+    micrograph of both (median of `runs`, output on the same tmpfs) and the device time of the particle kernels in both (library
+    profiler, in process).  The stack threshold is the score that keeps n_picks picks per micrograph of the table `extract`
+    writes, so both legs cut the pick count the rest of this tool uses.  two_root: the source tree whose `python -m topaz_amd`
+    runs the two-command leg (a checkout of the parent commit, to measure against the code before the fused command)."""
+    EXTRACT = extract_args.split()
+    import pandas as pd
+    from topaz_amd import runtime as rt
+    from topaz_amd.main import main as topaz
+    mics = [os.path.join(d, f'mic{i}.mrc') for i in range(n_mics)]
+    table = os.path.join(d, 'extract_picks.txt')
+    stack_args = ['--size', str(S)] + (['--resize', str(R)] if R != S else [])
+    fused_args = ['--particle-size', str(S)] + (['--particle-resize', str(R)] if R != S else [])
+    _cli(['extract'] + EXTRACT + ['-o', table] + mics)                                   # warm-up (page cache, code objects)
+    scores = np.sort(pd.read_csv(table, sep='\t').score.values)[::-1]
+    kept = min(len(scores), n_picks * n_mics)
+    T = repr(float(scores[kept - 1]))
+    lines = [f'  extract {" ".join(EXTRACT)}: {len(scores)} picks in the table, {kept} with score >= {T} go into the stack']
+    two, one = [], []
+    for _ in range(runs):
+        t = _cli(['extract'] + EXTRACT + ['-o', table] + mics, two_root)
+        t += _cli(['particle_stack', table, '--image-root', d, '--threshold', T, '-o', os.path.join(d, 'two.mrcs')] + stack_args,
+                  two_root)
+        two.append(t / n_mics * 1e3)
+        one.append(_cli(['extract'] + EXTRACT + ['-o', os.path.join(d, 'fused_picks.txt'), '--particle-stack',
+                                                 os.path.join(d, 'fused.mrcs'), '--particle-threshold', T] + fused_args + mics)
+                   / n_mics * 1e3)
+    import filecmp
+    same = filecmp.cmp(os.path.join(d, 'two.mrcs'), os.path.join(d, 'fused.mrcs'), shallow=False)
+    lines.append(f'  CLI wall time, extract then particle_stack: median {np.median(two):.1f} ms per micrograph '
+                 f'({min(two):.1f} .. {max(two):.1f}, {runs} runs)')
+    lines.append(f'  CLI wall time, extract --particle-stack:    median {np.median(one):.1f} ms per micrograph '
+                 f'({min(one):.1f} .. {max(one):.1f}, {runs} runs); stacks byte-identical: {same}')
+    # device time of the particle kernels, in process: the fused command launches what particle_stack launches
+    ctx = rt.get_context(0)
+    for label, argv in (('particle_stack', ['particle_stack', table, '--image-root', d, '--threshold', T, '-o',
+                                            os.path.join(d, 'two.mrcs')] + stack_args),
+                        ('extract --particle-stack', ['extract'] + EXTRACT + ['-o', os.path.join(d, 'fused_picks.txt'),
+                                                      '--particle-stack', os.path.join(d, 'fused.mrcs'), '--particle-threshold', T]
+                         + fused_args + mics)):
+        topaz(argv)                                                                          # warm-up
+        ctx.prof_enable(1)
+        ctx.prof_reset()
+        topaz(argv)
+        ctx.sync()
+        ms, n = _particle_kernels(ctx, n_mics)
+        ctx.prof_enable(0)
+        lines.append(f'  particle kernels in {label}: {ms:.3f} ms per micrograph, {n} launches')
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mics', type=int, default=8)
@@ -110,6 +181,10 @@ def main():
     ap.add_argument('--resize', type=int, default=128)
     ap.add_argument('--cpu-runs', type=int, default=3)
     ap.add_argument('--tmp', default='/dev/shm' if os.path.isdir('/dev/shm') else None)
+    ap.add_argument('--fused', action='store_true', help='also measure extract --particle-stack against extract + particle_stack')
+    ap.add_argument('--fused-only', action='store_true', help='only that')
+    ap.add_argument('--extract-args', default=EXTRACT, help='the extract flags of the fused leg')
+    ap.add_argument('--two-command-root', default=ROOT, help='source tree that runs the two-command leg (default: this one)')
     a = ap.parse_args()
     d = tempfile.mkdtemp(prefix='particle_stack_', dir=a.tmp)
     try:
@@ -118,6 +193,14 @@ def main():
         for R in (a.size, a.resize):
             label = f'S = {a.size}' + (f' -> R = {R}' if R != a.size else '')
             print(f'\n== {label}')
+            if a.fused or a.fused_only:
+                print(f'extract --particle-stack against extract + particle_stack (two-command leg from {a.two_command_root}):'
+                      if a.two_command_root != ROOT else 'extract --particle-stack against extract + particle_stack:')
+                for line in fused_leg(d, a.size, R, a.mics, a.picks, a.extract_args, a.two_command_root):
+                    print(line)
+                sys.stdout.flush()
+                if a.fused_only:
+                    continue
             print('device kernels (library profiler):')
             for line in device_kernels(picks, d, a.size, R, a.mics):
                 print(line)

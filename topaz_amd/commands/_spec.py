@@ -62,6 +62,19 @@ EXTRACT: List[Flag] = [
                                                                  '(`--alpha`)')),
     (('--preprocess-beta',), dict(type=float, default=1, help='--preprocess: beta of the Beta prior on the mixing proportion '
                                                               '(`--beta`)')),
+    (('--particle-stack',), dict(metavar='PATH',
+                                 help='also write the MRC particle stack `topaz particle_stack` would make of the pick table, and '
+                                      'its STAR file next to it, cut while each micrograph is resident for picking (under '
+                                      '--preprocess S -x S: from the raw frame).  The micrographs must be MRC files given sorted '
+                                      'by name; needs --particle-size, --dims 2 and a model, not with --targets')),
+    (('--particle-size',), dict(type=int, help='--particle-stack: box size in pixels (`particle_stack --size`)')),
+    (('--particle-resize',), dict(type=int, default=-1, help='--particle-stack: downsample every box to this size '
+                                                             '(`particle_stack --resize`; default: off)')),
+    (('--particle-threshold',), dict(type=float, default=-float('inf'),
+                                     help='--particle-stack: keep picks with score >= this in the stack (`particle_stack '
+                                          '--threshold`; default: -inf).  The pick table is not filtered by it')),
+    (('--particle-metadata',), dict(metavar='STAR', help='--particle-stack: per-micrograph metadata merged into the output STAR '
+                                                         '(`particle_stack --metadata`)')),
 ]
 
 _TRAINING_ONLY = 'training option (not supported on this path)'
@@ -185,6 +198,9 @@ PARTICLE_STACK: List[Flag] = [
     (('--image-ext',), dict(default='.mrc', help='extension appended to the image names (default: .mrc)')),
     (('--metadata',), dict(help='STAR file of per-micrograph metadata merged into the output STAR on MicrographName')),
 ]
+# kept apart from the table above, which mirrors the reference's parser flag for flag (tests/test_cpu_particle_stack.py): the
+# ranks cut the plan's micrographs i = rank (mod N) into the one output file
+PARTICLE_STACK_RANKS: List[Flag] = [_GPUS]
 
 
 def build_parser(flags: List[Flag], description: str, parser: argparse.ArgumentParser = None) -> argparse.ArgumentParser:

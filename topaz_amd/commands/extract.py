@@ -19,6 +19,13 @@ def main(args):
     if scale < 0:
         raise ValueError(f'--preprocess {scale}: a reduction factor >= 1, or 0 for off')
     check_preprocess_args(scale, args.model, args.dims)
+    from ..utils.picks import check_particle_stack_args
+    stack = dict(particle_stack=getattr(args, 'particle_stack', None), particle_size=getattr(args, 'particle_size', None),
+                 particle_resize=getattr(args, 'particle_resize', -1),
+                 particle_threshold=getattr(args, 'particle_threshold', -float('inf')),
+                 particle_metadata=getattr(args, 'particle_metadata', None))
+    check_particle_stack_args(stack['particle_stack'], stack['particle_size'], stack['particle_resize'], args.model, args.dims,
+                              args.targets, args.only_validate)
     preprocess = None
     if scale:
         from ..stats import DevicePreprocess
@@ -29,7 +36,7 @@ def main(args):
                       args.targets, args.min_radius, args.max_radius, args.step_radius, args.assignment_radius,
                       args.patch_size, args.only_validate, args.output, args.per_micrograph, args.suffix, args.format,
                       args.up_scale, args.down_scale, dims=args.dims, verbose=args.verbose,
-                      precision_check=getattr(args, 'precision_check', 'auto'), preprocess=preprocess)
+                      precision_check=getattr(args, 'precision_check', 'auto'), preprocess=preprocess, **stack)
 
 
 if __name__ == '__main__':

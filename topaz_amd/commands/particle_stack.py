@@ -6,8 +6,10 @@ help = 'extract mrc particle stack given coordinates table'
 
 
 def add_arguments(parser=None):
-    from ._spec import PARTICLE_STACK, build_parser
-    return build_parser(PARTICLE_STACK, help, parser)
+    from ._spec import PARTICLE_STACK, PARTICLE_STACK_RANKS, build_parser
+    # the parser of the command alone is the reference's flag surface; under the `topaz` entry point, whose launcher starts the
+    # rank processes, it also takes --gpus
+    return build_parser(PARTICLE_STACK + (PARTICLE_STACK_RANKS if parser is not None else []), help, parser)
 
 
 def main(args):

@@ -10,6 +10,8 @@ stream_inputs :259-263, extract_particles :266-367) -- over a different engine:
   suppression    tpz_nms_2d / _3d on the device map; only the pick table crosses PCIe.
   RadiusSearch   `--targets`: score maps cached on the device once, one device NMS + one Hungarian matching per radius.
   PickSink       the three output shapes (one TSV, per-micrograph tables, stdout).
+  ExtractStack   `--particle-stack` (utils/picks.py): the boxes around a micrograph's picks, cut from the image the feed decoded
+                 while it is still resident and streamed into the MRC stack `topaz particle_stack` would write.
 
 Differences from the reference, all deliberate: there is no CPU path (`device` < 0 raises); worker pools are accepted and
 ignored (the suppression is on the GPU); with WORLD_SIZE > 1 the micrographs are dealt round-robin to the ranks and the
@@ -371,27 +373,43 @@ class Scorer:
 
 def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int = 0, batch_size: int = 1,
                  keep_on_device: bool = False, precision_check: str = 'never',
-                 verbose: bool = False, preprocess=None) -> Iterator[Tuple[str, np.ndarray]]:
+                 verbose: bool = False, preprocess=None, with_image: bool = False) -> Iterator[Tuple[str, np.ndarray]]:
     """generator of (path, score map).  `model` None / 'none': the inputs already are score maps and pass through.
     keep_on_device=True yields device tensors (no PCIe round trip before the suppression).  precision_check / verbose: the
     `--precision-check` mode of the loaded model (Scorer).  preprocess: a callable device tensor -> device tensor (e.g.
     stats.DevicePreprocess) applied to every image the feed yields before it is scored -- here, in the consuming thread and in
-    path order, so whatever it draws from the NumPy RNG is drawn in the order `topaz preprocess` draws it."""
+    path order, so whatever it draws from the NumPy RNG is drawn in the order `topaz preprocess` draws it.
+    with_image=True: items are (path, score map, image, MRC header or None) -- image is the device tensor the feed decoded from
+    the file, BEFORE `preprocess`; it aliases a staging slot and is valid until the consumer asks for the next item."""
     paths = list(paths)
     if model is None or model == 'none':
         if preprocess is not None:
             raise ValueError('preprocess needs a model: score maps are not micrographs')
+        if with_image:
+            raise ValueError('with_image needs a model: score maps are not micrographs')
         for path in paths:
             yield path, load_image(path, make_image=False, return_header=False)
         return
     scorer = Scorer(model, device, precision_check, verbose)
-    for path, image in ImageFeed(paths, scorer.ctx):
-        if preprocess is not None:
-            image = preprocess(image)
+    for item in (ImageFeed(paths, scorer.ctx, headers=True) if with_image else ImageFeed(paths, scorer.ctx)):
+        path, raw = item[0], item[1]
+        image = raw if preprocess is None else preprocess(raw)
         scores = scorer(image, patch_size)
         if torch.is_tensor(scores) and not keep_on_device:
             scores = scores.cpu().numpy()
+        if with_image:
+            yield path, scores, raw, item[2]
+        else:
+            yield path, scores
+
+
+def _keep_resident(items, resident: list):
+    """(path, score map) of score_images(with_image=True) items, for the suppression; the image and the header of the item being
+    worked on are left in `resident` -- replaced, not collected: the tensor is only valid until the next item is asked for"""
+    for path, scores, image, header in items:
+        resident[:] = [image, header]
         yield path, scores
+    resident[:] = []
 
 
 def check_preprocess_args(preprocess, model, dims) -> None:
@@ -477,12 +495,19 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
                       num_workers: int, targets: str, min_radius: int, max_radius: int, step: int, match_radius: int,
                       patch_size, only_validate: bool, output: str, per_micrograph: bool, suffix: str, out_format: str,
                       up_scale: float, down_scale: float, dims=2, verbose: bool = False, precision_check: str = 'never',
-                      preprocess=None):
+                      preprocess=None, particle_stack: Optional[str] = None, particle_size: Optional[int] = None,
+                      particle_resize: int = -1, particle_threshold: float = -np.inf, particle_metadata: Optional[str] = None):
     """preprocess: None, or a callable device tensor -> device tensor (stats.DevicePreprocess) every micrograph goes through
     before it is scored (`--preprocess`).  Everything downstream -- patches, the radius search, the ranks, the outputs -- sees
     the smaller, normalised image only: picks are in ITS frame, as they are when `topaz preprocess` wrote it to a file first;
-    up_scale / down_scale move them, as ever."""
+    up_scale / down_scale move them, as ever.
+    particle_stack: also write the MRC particle stack (and its STAR file) `topaz particle_stack` would make of the pick table:
+    particle_size boxes (particle_resize: down-sampled to that size) around the picks with score >= particle_threshold, cut at
+    the coordinates the table holds from the image the feed decoded -- under `preprocess` the raw frame -- while it is resident
+    (utils.picks.ExtractStack).  The pick table itself is what it is without the stack."""
+    from .utils import picks as pk
     check_preprocess_args(preprocess, model, dims)               # (before anything is loaded)
+    pk.check_particle_stack_args(particle_stack, particle_size, particle_resize, model, dims, targets, only_validate)
     report('Beginning extraction')
     rank, local_rank, world = parallel.init_from_env()
     if world > 1:
@@ -496,9 +521,18 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
             paths = list(stream_inputs(f))
     else:
         paths = list(stream_inputs(sys.stdin))
+    stack = None
+    if particle_stack:
+        pk.check_particle_stack_inputs(paths)                    # (still nothing loaded)
+        stack = pk.ExtractStack(particle_stack, particle_size, particle_resize, particle_threshold, particle_metadata,
+                                (rank, local_rank, world))
     mine = parallel.shard_indices(len(paths), rank, world)
     maps = score_images(model, [paths[i] for i in mine], device=device, patch_size=patch_size, batch_size=batch_size,
-                        keep_on_device=True, precision_check=precision_check, verbose=verbose, preprocess=preprocess)
+                        keep_on_device=True, precision_check=precision_check, verbose=verbose, preprocess=preprocess,
+                        with_image=stack is not None)
+    resident: list = []                                          # the image (and header) behind the score map being suppressed
+    if stack is not None:
+        maps = _keep_resident(maps, resident)
     radius = -1 if radius is None else radius
 
     if targets is not None:
@@ -532,5 +566,18 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
             if scale != 1:
                 coords = np.round(coords * scale).astype(int)
             sink.add(mine[k], path, scores, coords)
+            if stack is not None:
+                try:
+                    stack.add(mine[k], path, resident[0], resident[1], scores, coords)
+                except BaseException:
+                    stack.discard()
+                    raise
+        if stack is not None:
+            for _ in range(len(mine), -(-len(paths) // world)):   # a ragged last round: the ranks without an image take part
+                stack.skip_round()
         sink.finish(paths, rank, world, local_rank)
+        if stack is not None:
+            n = stack.finish(paths)
+            if verbose and rank == 0:
+                report(f'Wrote {n} particles to {particle_stack}')
     report('Extraction complete')

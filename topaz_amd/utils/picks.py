@@ -6,7 +6,13 @@ the host and fixes everything that does not depend on pixel values -- the partic
 and refuses bad input before a byte is written.  write_particle_stack then streams the micrographs through the MI355X
 (extract.ImageFeed: micrograph i+1 is decoded and uploaded while micrograph i is cropped), cuts the boxes in chunks that fit a
 device byte budget (tpz_particle_stack: one launch per chunk, four with --resize) and hands each chunk through a pinned staging
-slot to a writer thread, so the stack is written once, in order, and never held whole on the host.
+slot to a writer thread, so the stack is written once and never held whole on the host.
+
+Both halves are shared with `topaz extract --particle-stack` (ExtractStack), which cuts the boxes of a micrograph while it is
+resident for picking: plan_from_records builds the header and the STAR text from picks held in memory, StackWriter is the
+streaming half.  A chunk goes to the byte its first particle's index fixes (os.pwrite) and the header is written last, so the
+ranks of `--gpus N` write one file -- each its share of the plan's micrographs here, each its share of the input list there --
+and a stack whose length is only known after the last micrograph needs no second pass.  Output is byte-identical to one process.
 
 Divergences from the reference, all deliberate:
   - --resize: the reference hands the 3-D (mz, S, S) box to its 2-D `downsample`, whose concatenation then joins frames instead
@@ -22,7 +28,7 @@ from __future__ import annotations
 import io
 import os
 import sys
-from typing import List, NamedTuple, Optional
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -53,14 +59,62 @@ class Plan(NamedTuple):
     star: str                   # the STAR file's text
 
 
+class Record(NamedTuple):
+    """the kept picks of one micrograph, in memory: what the stack header and the STAR text are built from"""
+    name: str                   # MicrographName
+    xy: np.ndarray              # [n, 2] integer (x, y), in table order
+    scores: Optional[np.ndarray]  # float64 [n], or None for a table without a score column
+
+
 def _header_of(path: str):
     with open(path, 'rb') as f:
         return mrc.parse_header(f.read(1024))
 
 
+def check_boxes(name: str, xy: np.ndarray, size: int) -> None:
+    """a box wholly outside the low edge of the micrograph has no crop (the reference crashes there): ValueError"""
+    x, y = xy[:, 0], xy[:, 1]
+    bad = np.flatnonzero((x - size // 2 + size < 0) | (y - size // 2 + size < 0))
+    if bad.size:
+        j = int(bad[0])
+        raise ValueError(f'particle_stack: pick ({x[j]}, {y[j]}) of {name}: its {size}-pixel box lies wholly outside the '
+                         'low edge of the micrograph')
+
+
+def plan_from_records(records: Sequence[Record], output_file: str, size: int, resize: int, mz: int, cella, cellb,
+                      metadata_file: Optional[str]):
+    """(stack header bytes, STAR path, STAR text) of the particles in `records`, in that order -- the half of the planner that
+    does not care where the picks came from: `particle_stack` reads them from a table, `extract --particle-stack` has them in
+    memory.  resize: the written box size (== size when off); cella / cellb: of the first micrograph's header."""
+    N = int(sum(len(r.xy) for r in records))
+    header = mrc.header_struct.pack(*list(mrc.make_header((N * mz, resize, resize), cella, cellb, mz=mz, dtype=np.float32)))
+
+    stack_name = os.path.basename(output_file)
+    star_path = os.path.splitext(output_file)[0] + '.star'
+    names = [r.name for r in records for _ in range(len(r.xy))]
+    table = {'MicrographName': names, 'CoordinateX': np.concatenate([np.asarray(r.xy)[:, 0] for r in records]),
+             'CoordinateY': np.concatenate([np.asarray(r.xy)[:, 1] for r in records])}
+    if records[0].scores is not None:
+        table['AutopickFigureOfMerit'] = np.concatenate([np.asarray(r.scores, dtype=np.float64) for r in records])
+    metadata = pd.DataFrame(table)
+    metadata['ImageName'] = [str(i + 1) + '@' + stack_name for i in range(len(metadata))]
+    if mz > 1:
+        metadata['NrOfFrames'] = mz
+    if metadata_file is not None:
+        with open(metadata_file, 'r') as f:
+            metadata = pd.merge(metadata, read_star(f), on='MicrographName', how='left')
+    if resize != size and 'DetectorPixelSize' in metadata:
+        metadata['DetectorPixelSize'] = metadata['DetectorPixelSize'].values.astype(float) * (size / resize)
+    buf = io.StringIO()
+    write_star(metadata, buf)
+    return header, star_path, buf.getvalue()
+
+
 def plan_particle_stack(input_file: str, output_file: str, threshold: float, size: Optional[int], resize: int,
-                        image_root: Optional[str], image_ext: str, metadata_file: Optional[str], log=sys.stderr) -> Plan:
-    """everything of create_particle_stack but the pixels; raises ValueError / FileNotFoundError on bad input"""
+                        image_root: Optional[str], image_ext: str, metadata_file: Optional[str], log=None) -> Plan:
+    """everything of create_particle_stack but the pixels; raises ValueError / FileNotFoundError on bad input.
+    log: where the progress lines go (default: sys.stderr as it is at the call, not at import)"""
+    log = sys.stderr if log is None else log
     if size is None:
         raise ValueError('particle_stack: --size is required')
     if size < 1:
@@ -84,7 +138,7 @@ def plan_particle_stack(input_file: str, output_file: str, threshold: float, siz
         if not np.issubdtype(particles[col].dtype, np.integer):
             raise ValueError(f'particle_stack: {col} must hold integer pixel coordinates')
 
-    micrographs, names, xs, ys, scores = [], [], [], [], []
+    micrographs, records = [], []
     mz = cella = cellb = None
     for image_name, coords in particles.groupby('image_name'):
         name = str(image_name) + image_ext
@@ -100,40 +154,14 @@ def plan_particle_stack(input_file: str, output_file: str, threshold: float, siz
             cella, cellb = (h.xlen, h.ylen, h.zlen), (h.alpha, h.beta, h.gamma)
         elif z != mz:
             raise ValueError(f'particle_stack: {path} has {z} frames, the first micrograph {mz}')
-        x = coords['x_coord'].values
-        y = coords['y_coord'].values
-        bad = np.flatnonzero((x - size // 2 + size < 0) | (y - size // 2 + size < 0))
-        if bad.size:
-            j = int(bad[0])
-            raise ValueError(f'particle_stack: pick ({x[j]}, {y[j]}) of {name}: its {size}-pixel box lies wholly outside the '
-                             'low edge of the micrograph')
-        micrographs.append(Micrograph(str(image_name), name, path, np.stack([x, y], 1).astype(np.int32),
+        xy = np.stack([coords['x_coord'].values, coords['y_coord'].values], 1)
+        check_boxes(name, xy, size)
+        micrographs.append(Micrograph(str(image_name), name, path, xy.astype(np.int32),
                                       (h.ny, h.nx) if z == 1 else (z, h.ny, h.nx)))
-        names += [name] * len(coords)
-        xs.append(x)
-        ys.append(y)
-        if 'score' in coords:
-            scores.append(coords['score'].values)
+        records.append(Record(name, xy, coords['score'].values if 'score' in coords else None))
 
-    header = mrc.header_struct.pack(*list(mrc.make_header((N * mz, resize, resize), cella, cellb, mz=mz, dtype=np.float32)))
-
-    stack_name = os.path.basename(output_file)
-    star_path = os.path.splitext(output_file)[0] + '.star'
-    table = {'MicrographName': names, 'CoordinateX': np.concatenate(xs), 'CoordinateY': np.concatenate(ys)}
-    if 'score' in particles:
-        table['AutopickFigureOfMerit'] = np.concatenate(scores)
-    metadata = pd.DataFrame(table)
-    metadata['ImageName'] = [str(i + 1) + '@' + stack_name for i in range(len(metadata))]
-    if mz > 1:
-        metadata['NrOfFrames'] = mz
-    if metadata_file is not None:
-        with open(metadata_file, 'r') as f:
-            metadata = pd.merge(metadata, read_star(f), on='MicrographName', how='left')
-    if resize != size and 'DetectorPixelSize' in metadata:
-        metadata['DetectorPixelSize'] = metadata['DetectorPixelSize'].values.astype(float) * (size / resize)
-    buf = io.StringIO()
-    write_star(metadata, buf)
-    return Plan(output_file, star_path, size, resize, mz, N, micrographs, header, buf.getvalue())
+    header, star_path, star = plan_from_records(records, output_file, size, resize, mz, cella, cellb, metadata_file)
+    return Plan(output_file, star_path, size, resize, mz, N, micrographs, header, star)
 
 
 def resize_operators(size: int, resize: int) -> np.ndarray:
@@ -148,77 +176,323 @@ def resize_operators(size: int, resize: int) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([cols.ravel(), rows.ravel()]).astype(np.float32))
 
 
-def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAULT_BUDGET, log=sys.stderr) -> None:
-    """cut, standardise (and resize) the planned particles on the MI355X and write the stack and the STAR file"""
-    import queue
-    import threading
+def particle_offset(base: int, counts: Sequence[int], rank: int) -> Tuple[int, int]:
+    """One round of a sharded `extract --particle-stack`: the ranks hold the micrographs round * world + r and `counts[r]` is the
+    number of particles rank r keeps of its one (0: none kept, or no micrograph left in a ragged last round).  Input order is
+    rank order within the round, so with `base` particles in the rounds before, rank `rank` writes from particle
+    base + sum(counts[:rank]) on.  Returns (that index, the base of the next round)."""
+    counts = [int(c) for c in counts]
+    return base + sum(counts[:rank]), base + sum(counts)
 
+
+class StackWriter:
+    """The streaming half of a particle stack, shared by `particle_stack` and `extract --particle-stack`.  cut() crops,
+    standardises (and resizes) the picks of one resident micrograph in chunks of the device byte budget and hands every chunk
+    through a slot of a pinned rt.Stage ring to a writer thread.  The thread puts the chunk at the byte the global index of its
+    first particle fixes (os.pwrite): the ranks of a sharded job write one file, and a stack whose length is only known after the
+    last micrograph gets its header last (seal_particle_stack).  Every rank opens the same file and none truncates it."""
+
+    DEPTH = 2
+
+    def __init__(self, ctx, path: str, size: int, resize: int, mz: int, budget_bytes: int = DEFAULT_BUDGET, capacity: int = 0,
+                 placeholder: bool = True):
+        """capacity: particles per ring slot to start with (it grows to the largest chunk seen); placeholder: write the 1024
+        bytes the header will replace (rank 0)"""
+        import queue
+        import threading
+        self.ctx, self.path, self.S, self.R, self.mz = ctx, path, size, resize, mz
+        self.ops = resize_operators(size, resize) if resize != size else None
+        self.out_bytes = 4 * mz * resize * resize
+        dev_bytes = self.out_bytes + (4 * mz * (size * size + 2 * size * resize) if resize != size else 0)
+        self.per_chunk = max(1, int(budget_bytes) // dev_bytes)
+        self.stage = None
+        self.capacity = 0
+        self.free_slots: 'queue.Queue' = queue.Queue()
+        self.todo: 'queue.Queue' = queue.Queue()
+        self.failed: list = []
+        self.fd = os.open(path, os.O_WRONLY | os.O_CREAT, 0o666)
+        if placeholder:
+            os.pwrite(self.fd, bytes(1024), 0)
+        if capacity:
+            self._ensure(min(self.per_chunk, capacity))
+        self.thread = threading.Thread(target=self._writer, daemon=True)
+        self.thread.start()
+
+    def _ensure(self, n: int) -> None:
+        """a ring whose slots hold n particles"""
+        from .. import runtime as rt
+        if n <= self.capacity:
+            return
+        if self.stage is not None:
+            for _ in range(self.DEPTH):                         # every chunk in flight has been written
+                self.free_slots.get()
+            self.stage.close()
+            self.stage = None
+            self.check()
+        self.capacity = n
+        self.stage = rt.Stage(self.ctx, n * self.out_bytes, self.DEPTH)
+        for k in range(self.DEPTH):
+            self.free_slots.put(k)
+
+    def _writer(self) -> None:
+        while True:
+            item = self.todo.get()
+            if item is None:
+                return
+            k, n_floats, at, _device_chunk = item               # (the tensor lives until its copy has landed)
+            try:
+                if not self.failed:
+                    self.stage.wait(k)
+                    view = memoryview(self.stage.host_array(k, (n_floats,))).cast('B')
+                    done = 0
+                    while done < len(view):
+                        done += os.pwrite(self.fd, view[done:], at + done)
+            except BaseException as e:                          # surfaces in the main thread
+                self.failed.append(e)
+            finally:
+                self.free_slots.put(k)
+
+    def check(self) -> None:
+        if self.failed:
+            raise self.failed[0]
+
+    def cut(self, img, xy: np.ndarray, first: int) -> None:
+        """the particles at xy ([n, 2] int32) of the resident micrograph img are particles first .. first + n - 1 of the stack"""
+        from .. import runtime as rt
+        for c0 in range(0, len(xy), self.per_chunk):
+            part = xy[c0:c0 + self.per_chunk]
+            self._ensure(len(part))
+            out = rt.particle_stack(img, part, self.S, self.R, self.ops, ctx=self.ctx)
+            k = self.free_slots.get()
+            self.check()
+            self.stage.download(k, out)
+            self.todo.put((k, out.numel(), 1024 + self.out_bytes * (first + c0), out))
+
+    def close(self) -> None:
+        """wait for the last write, free the ring, close the file (idempotent; a writer failure stays in `failed`)"""
+        if self.thread is None:
+            return
+        self.todo.put(None)
+        self.thread.join()
+        self.thread = None
+        if self.stage is not None:
+            self.stage.close()
+            self.stage = None
+        os.close(self.fd)
+
+
+def seal_particle_stack(path: str, header: bytes, n: int, out_bytes: int, star_path: str, star: str) -> None:
+    """what rank 0 does last: the header over the placeholder, the file cut to its n particles, the STAR file"""
+    fd = os.open(path, os.O_WRONLY)
+    try:
+        os.pwrite(fd, header, 0)
+        os.ftruncate(fd, 1024 + n * out_bytes)
+    finally:
+        os.close(fd)
+    with open(star_path, 'w') as f:
+        f.write(star)
+
+
+def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAULT_BUDGET, log=None,
+                         ranks: Tuple[int, int, int] = (0, 0, 1)) -> None:
+    """cut, standardise (and resize) the planned particles on the MI355X and write the stack and the STAR file.
+    ranks: (rank, local_rank, world) of a sharded job -- this rank takes the plan's micrographs i = rank (mod world); the plan
+    holds every count, so each micrograph's place in the file is known up front."""
     import torch
 
+    from .. import parallel
     from .. import runtime as rt
     from ..extract import ImageFeed
+    log = sys.stderr if log is None else log
+    rank, local_rank, world = ranks
     torch.cuda.set_device(device)
     ctx = rt.get_context(device)
-    S, R, mz = plan.size, plan.resize, plan.mz
-    ops = resize_operators(S, R) if R != S else None
-    out_bytes = 4 * mz * R * R
-    dev_bytes = out_bytes + (4 * mz * (S * S + 2 * S * R) if R != S else 0)
-    per_chunk = max(1, min(int(budget_bytes) // dev_bytes, max(len(m.xy) for m in plan.micrographs)))
-    DEPTH = 2
-    stage = rt.Stage(ctx, per_chunk * out_bytes, DEPTH)
-    free_slots: 'queue.Queue' = queue.Queue()
-    for k in range(DEPTH):
-        free_slots.put(k)
-    todo: 'queue.Queue' = queue.Queue()
-    failed: list = []
-
-    with open(plan.output, 'wb') as f:
-        f.write(plan.header)
-
-        def writer():
-            while True:
-                item = todo.get()
-                if item is None:
-                    return
-                k, n_floats, _device_chunk = item               # (the tensor lives until its copy has landed)
-                try:
-                    if not failed:
-                        stage.wait(k)
-                        f.write(memoryview(stage.host_array(k, (n_floats,))).cast('B'))
-                except BaseException as e:                      # surfaces in the main thread
-                    failed.append(e)
-                finally:
-                    free_slots.put(k)
-
-        th = threading.Thread(target=writer, daemon=True)
-        th.start()
-        try:
-            for m, (path, img) in zip(plan.micrographs, ImageFeed([m.path for m in plan.micrographs], ctx)):
-                if tuple(img.shape) != tuple(m.shape):
-                    raise ValueError(f'particle_stack: {path} holds {tuple(img.shape)} pixels, its header says {m.shape}')
-                print('#', m.label, len(m.xy), 'particles', file=log)
-                for c0 in range(0, len(m.xy), per_chunk):
-                    xy = m.xy[c0:c0 + per_chunk]
-                    out = rt.particle_stack(img, xy, S, R, ops, ctx=ctx)
-                    k = free_slots.get()
-                    if failed:
-                        raise failed[0]
-                    stage.download(k, out)
-                    todo.put((k, out.numel(), out))
-        finally:
-            todo.put(None)
-            th.join()
-            stage.close()
-        if failed:
-            raise failed[0]
-    with open(plan.star_path, 'w') as f:
-        f.write(plan.star)
+    firsts = np.concatenate([[0], np.cumsum([len(m.xy) for m in plan.micrographs])])
+    mine = parallel.shard_indices(len(plan.micrographs), rank, world)
+    mics = [plan.micrographs[i] for i in mine]
+    writer = StackWriter(ctx, plan.output, plan.size, plan.resize, plan.mz, budget_bytes,
+                         capacity=max([len(m.xy) for m in mics] or [0]), placeholder=(rank == 0))
+    try:
+        for j, (path, img) in enumerate(ImageFeed([m.path for m in mics], ctx)):
+            m = mics[j]
+            if tuple(img.shape) != tuple(m.shape):
+                raise ValueError(f'particle_stack: {path} holds {tuple(img.shape)} pixels, its header says {m.shape}')
+            print('#', m.label, len(m.xy), 'particles', file=log)
+            writer.cut(img, m.xy, int(firsts[mine[j]]))
+    finally:
+        writer.close()
+    writer.check()
+    if world > 1:
+        parallel.barrier(parallel.collective_device(local_rank))       # every rank's particles are in the file
+    if rank == 0:
+        seal_particle_stack(plan.output, plan.header, plan.n, writer.out_bytes, plan.star_path, plan.star)
 
 
 def create_particle_stack(input_file: str, output_file: str, threshold: float, size: Optional[int], resize: int,
                           image_root: Optional[str], image_ext: str, metadata_file: Optional[str], device: int = 0,
                           budget_bytes: int = DEFAULT_BUDGET) -> Plan:
-    """topaz/utils/picks.py:71-197 on the MI355X; budget_bytes: device bytes of one chunk of particles"""
-    plan = plan_particle_stack(input_file, output_file, threshold, size, resize, image_root, image_ext, metadata_file)
-    write_particle_stack(plan, device=device, budget_bytes=budget_bytes)
+    """topaz/utils/picks.py:71-197 on the MI355X; budget_bytes: device bytes of one chunk of particles.  Under `--gpus N`
+    (WORLD_SIZE > 1) every rank plans the whole table and cuts its share of the micrographs into the one output file."""
+    from .. import parallel
+    under_ranks = int(os.environ.get('WORLD_SIZE', '1')) > 1
+    quiet = under_ranks and int(os.environ.get('RANK', '0')) != 0
+    plan = plan_particle_stack(input_file, output_file, threshold, size, resize, image_root, image_ext, metadata_file,
+                               **({'log': io.StringIO()} if quiet else {}))
+    ranks = parallel.init_from_env() if under_ranks else (0, 0, 1)      # (after the plan: bad input fails before the rendezvous)
+    if ranks[2] > 1:
+        device = parallel.rank_device(ranks[1])
+    write_particle_stack(plan, device=device, budget_bytes=budget_bytes, ranks=ranks,
+                         **({'log': io.StringIO()} if quiet else {}))
     return plan
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# `extract --particle-stack`: the stack written while the micrographs are resident for picking
+# ---------------------------------------------------------------------------------------------------------------------
+def check_particle_stack_args(output, size, resize, model, dims, targets, only_validate) -> None:
+    """`extract --particle-stack` cuts 2-D boxes from the micrograph a network has just scored: refused without a box size, for
+    tomograms, for inputs that already are score maps and for the `--targets` modes (they keep score maps resident, not images).
+    Raises ValueError; touches neither the GPU nor a model file."""
+    if not output:
+        return
+    if size is None:
+        raise ValueError('--particle-stack needs --particle-size (the box size in pixels)')
+    if size < 1:
+        raise ValueError(f'--particle-stack: --particle-size must be positive, got {size}')
+    if resize == 0 or resize > size:
+        raise ValueError(f'--particle-stack: --particle-resize must lie in 1..{size} (only downsampling), got {resize}')
+    if dims != 2:
+        raise ValueError('--particle-stack works on micrographs (--dims 2): a particle is a 2-D box')
+    if model is None or model == 'none':
+        raise ValueError('--particle-stack needs a model (-m): with -m none the inputs are score maps, not micrographs')
+    if targets is not None or only_validate:
+        raise ValueError('--particle-stack does not go with --targets / --only-validate: they keep every score map resident, '
+                         'not the micrographs')
+
+
+def check_particle_stack_inputs(paths: Sequence[str]) -> None:
+    """`particle_stack` orders the particles by sorted micrograph name; `extract` processes its inputs as given.  Rather than
+    reorder the extraction, a list whose names (basename without extension) are not strictly increasing in plain string order
+    is refused -- which refuses duplicate names too; a shell glob always passes.  The inputs must be MRC files."""
+    last = None
+    for p in paths:
+        name, ext = os.path.splitext(os.path.basename(p))
+        if ext != '.mrc':
+            raise ValueError(f'--particle-stack cuts boxes from MRC micrographs (.mrc); got {p}')
+        if last is not None and not last < name:
+            raise ValueError(f'--particle-stack: pass the micrographs sorted by name, each once ({name!r} comes after {last!r}): '
+                             'the stack holds the particles in the order `topaz particle_stack` writes them, by sorted name')
+        last = name
+
+
+def scores_as_read_back(xy: np.ndarray, scores: np.ndarray) -> np.ndarray:
+    """float64 [n]: the scores `particle_stack` reads back from the rows `extract` writes for these picks.  The table holds a
+    float32 score with the digits of its float64 value (tpz_format_picks), but pandas' default float parser is not correctly
+    rounded -- about one score in eight comes back one unit in the last place off, and prints as other digits in the STAR file.
+    So the value is made the way the two-command flow makes it: the same text through the same parser."""
+    from .files import format_pick_rows
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    if len(scores) == 0:
+        return np.zeros(0, np.float64)
+    text = format_pick_rows('m', np.asarray(xy).reshape(len(scores), -1)[:, :2], scores, 2)
+    return pd.read_csv(io.BytesIO(text), sep='\t', header=None, usecols=[3])[3].values.astype(np.float64)
+
+
+class ExtractStack:
+    """The particle stack of `topaz extract --particle-stack`: add() is called once per micrograph, in processing order, while
+    the image the feed decoded is still resident -- its kept picks are cut there and then (StackWriter) -- and finish() writes
+    the header and the STAR file once the number of particles is known.
+
+    With WORLD_SIZE > 1 the ranks advance in rounds of `world` micrographs: every add() (skip_round() for a rank the ragged last
+    round leaves without an image) is one tiny all_gather of the kept counts, from which each rank derives where its particles
+    go (particle_offset); finish() gathers the kept picks to rank 0 (parallel.gather_pick_tables), which writes the STAR."""
+
+    def __init__(self, output: str, size: int, resize: int, threshold: float, metadata_file: Optional[str],
+                 ranks: Tuple[int, int, int] = (0, 0, 1), budget_bytes: int = DEFAULT_BUDGET):
+        self.output, self.size, self.threshold, self.metadata_file = output, int(size), float(threshold), metadata_file
+        self.resize = self.size if resize < 0 else int(resize)
+        self.rank, self.local_rank, self.world = ranks
+        self.budget_bytes = budget_bytes
+        self.writer: Optional[StackWriter] = None
+        self.base = 0                                           # particles in the rounds so far
+        self.rows: list = []                                    # (input index, kept scores fp32, kept xy int32)
+        self.cell = None                                        # (cella, cellb) of the first micrograph
+        # a stack from an earlier run must not survive a run that fails
+        if self.rank == 0:
+            for p in (output, os.path.splitext(output)[0] + '.star'):
+                if os.path.exists(p):
+                    os.unlink(p)
+
+    def claim(self, n: int) -> int:
+        """the stack index of the first of the n particles this rank keeps of its micrograph of the current round"""
+        counts = [n]
+        if self.world > 1:
+            from .. import parallel
+            counts = parallel.gather_scalars(float(n), parallel.collective_device(self.local_rank))
+        first, self.base = particle_offset(self.base, counts, self.rank)
+        return first
+
+    def skip_round(self) -> None:
+        self.claim(0)
+
+    def add(self, index: int, path: str, image, header, scores, coords) -> int:
+        """micrograph `index` of the input list: image is the device tensor the feed decoded from `path`, header its MRC header,
+        (scores, coords) its pick table as written (coordinates after -x/-s).  Returns the number of particles cut."""
+        from .. import runtime as rt
+        if image.dim() != 2:
+            raise ValueError(f'--particle-stack: {path} holds {tuple(image.shape)} pixels; a micrograph is one 2-D image')
+        s32 = np.asarray(scores, dtype=np.float32).reshape(-1)
+        xy = np.zeros((0, 2), np.int32)
+        if len(s32):
+            xy = np.ascontiguousarray(np.asarray(coords).reshape(len(s32), -1)[:, :2], dtype=np.int32)
+        keep = scores_as_read_back(xy, s32) >= self.threshold
+        xy = np.ascontiguousarray(xy[keep])
+        check_boxes(os.path.basename(path), xy, self.size)
+        if index == 0:
+            self.cell = ((header.xlen, header.ylen, header.zlen), (header.alpha, header.beta, header.gamma))
+        first = self.claim(len(xy))
+        if self.writer is None:
+            self.writer = StackWriter(rt.get_context(image.device.index), self.output, self.size, self.resize, 1,
+                                      self.budget_bytes, placeholder=(self.rank == 0))
+        self.writer.cut(image, xy, first)
+        self.rows.append((index, s32[keep], xy))
+        return len(xy)
+
+    def close(self) -> None:
+        if self.writer is not None:
+            self.writer.close()
+
+    def discard(self) -> None:
+        """after a failure: no half-written stack stays behind"""
+        self.close()
+        if self.rank == 0 and os.path.exists(self.output):
+            os.unlink(self.output)
+
+    def finish(self, paths: Sequence[str]) -> int:
+        """every micrograph has been added: wait for the writes, then (rank 0) header and STAR.  Returns the stack length."""
+        import torch
+        self.close()
+        if self.writer is not None:
+            self.writer.check()
+        tables = {i: (s, xy) for i, s, xy in self.rows}
+        if self.world > 1:
+            from .. import parallel
+            # (a collective: every rank has closed its writer, so the gathered picks are all in the file)
+            got = parallel.gather_pick_tables([r[0] for r in self.rows], [torch.from_numpy(r[1]) for r in self.rows],
+                                              [torch.from_numpy(r[2]) for r in self.rows],
+                                              parallel.collective_device(self.local_rank))
+            if self.rank == 0:
+                tables = {i: (s.numpy(), c.numpy()) for i, (s, c) in got.items()}
+        n = self.base
+        if n == 0:
+            self.discard()
+            raise ValueError(f'--particle-stack: no particles left to extract at threshold {self.threshold}')
+        if self.rank == 0:
+            records = [Record(os.path.basename(paths[i]), tables[i][1], scores_as_read_back(tables[i][1], tables[i][0]))
+                       for i in sorted(tables) if len(tables[i][0])]
+            header, star_path, star = plan_from_records(records, self.output, self.size, self.resize, 1, self.cell[0],
+                                                        self.cell[1], self.metadata_file)
+            seal_particle_stack(self.output, header, n, 4 * self.resize * self.resize, star_path, star)
+        return n
+
+
