@@ -168,6 +168,11 @@ int tpz_affine(tpz_ctx* ctx, const float* d_x, size_t n, float scale, float shif
  * fp32 subtraction, then an IEEE fp32 division -- exact low bits on raw-count micrographs (|mean| >> std); std == 0 yields the
  * reference's inf / nan. */
 int tpz_normalize(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float std, float* d_y);
+/* tpz_normalize with the pixel cutoff of denoise_image fused (topaz/denoise.py:389-391): v = (x - mean) / std rounded as
+ * tpz_normalize rounds it, then v = 0 where v < -cutoff or v > cutoff, compared in fp32 (what numpy >= 2 does for a float32
+ * array and a Python float).  NaN passes through unchanged, +-inf (std == 0) is zeroed.  cutoff <= 0: no cutoff, the bytes of
+ * tpz_normalize.  Asynchronous; one launch. */
+int tpz_normalize_cutoff(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float std, float cutoff, float* d_y);
 /* 1->1 channel 2-D filter with zero "same" padding: GaussianDenoise / InvGaussianFilter /
  * AffineFilter.forward (topaz/filters.py:28-96).  h_w is the [k][k] kernel on the host. */
 int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_w, int k, float bias,

@@ -70,6 +70,7 @@ _SIGNATURES = {
     'tpz_normalize_f64': (C.c_int, [_P, _P, C.c_size_t, C.c_double, C.c_double, _P]),
     'tpz_affine': (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     'tpz_normalize': (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
+    'tpz_normalize_cutoff': (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
     'tpz_format_picks': (C.c_longlong, [C.c_char_p, _P, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_longlong]),
     'tpz_filter_2d': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P]),
     'tpz_lowpass_2d': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P]),

@@ -86,7 +86,8 @@ DENOISE: List[Flag] = [
     (('--suffix',), dict(default='', help='suffix of the output names')),
     (('--format',), dict(dest='format_', default='mrc', help='mrc, tiff, png or jpg')),
     (('--normalize',), dict(action='store_true', help='standardise the output instead of restoring mean and scale')),
-    (('--stack',), dict(action='store_true', help='the input is one MRC stack')),
+    (('--stack',), dict(action='store_true', help='the input is one MRC stack: every section is denoised on its own statistics and -o names '
+                                                    'the one output stack; --gpus shards the sections, all ranks writing that one file')),
     (('--save-prefix',), dict(help=_TRAINING_ONLY)),
     (('--save-interval',), dict(type=int, default=10, help=_TRAINING_ONLY)),
     (('-m', '--model'), dict(nargs='+', default=['unet'], help='one or more models (outputs averaged): unet, unet-small, fcnn, affine, unet-v0.2.1, or a file')),
@@ -100,7 +101,8 @@ DENOISE: List[Flag] = [
     (('--inv-gaussian',), dict(type=float, default=0, help='sigma of an inverse-Gaussian pre-filter')),
     (('--deconvolve',), dict(action='store_true', help='flatten the spatial covariance of the normalised micrograph before denoising')),
     (('--deconv-patch',), dict(type=int, default=1, help='estimate the --deconvolve filter per tile of an N x N grid (default: 1, the whole micrograph)')),
-    (('--pixel-cutoff',), dict(type=float, default=0, help='zero pixels further than this many sigma from the mean')),
+    (('--pixel-cutoff',), dict(type=float, default=0, help='zero pixels further than this many sigma from the mean before filtering and denoising '
+                                                                   '(0: keep every pixel)')),
     (('-s', '--patch-size'), dict(type=int, default=1024, help='tile size (<1: whole image)')),
     (('-p', '--patch-padding'), dict(type=int, default=500, help='halo around each tile')),
     (('--method',), dict(choices=['noise2noise', 'masked'], default='noise2noise', help=_TRAINING_ONLY)),

@@ -21,6 +21,8 @@ hipError_t launch_gmm_pass(const float* x, size_t n, int mode, const double* d_p
                            double* d_out, hipStream_t s);
 hipError_t launch_affine(const float* x, float* y, size_t n, float scale, float shift, hipStream_t s);
 hipError_t launch_normalize(const float* x, float* y, size_t n, float mu, float sd, hipStream_t s);     // y = (x - mu) / sd
+// y = (x - mu) / sd, then 0 where y < -c or y > c (fp32 comparisons; NaN passes); c <= 0: launch_normalize
+hipError_t launch_normalize_cutoff(const float* x, float* y, size_t n, float mu, float sd, float c, hipStream_t s);
 hipError_t launch_affine_dev(const float* x, int D, int H, int W, long long ps, int pitch, const float* d_p, float* y,
                              hipStream_t s);
 hipError_t launch_transpose(const float* in, float* out, int R, int Cc, hipStream_t s);

@@ -434,6 +434,25 @@ hipError_t launch_normalize(const float* x, float* y, size_t n, float mu, float 
     return hipGetLastError();
 }
 
+// The same with the pixel cutoff of denoise_image fused (denoise.py:389-391, `x[(x < -c) | (x > c)] = 0`): v rounded exactly as
+// normalize_kernel rounds it, then zeroed where v < -c or v > c, both comparisons in fp32 (numpy >= 2 compares a float32 array
+// with a Python float at float32).  NaN fails both comparisons and passes through; +-inf (std == 0) is zeroed.  c > 0.
+__global__ __launch_bounds__(256) void normalize_cutoff_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n,
+                                                               float mu, float sd, float c) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float v = __fdiv_rn(__fsub_rn(x[i], mu), sd);
+        y[i] = (v < -c || v > c) ? 0.0f : v;
+    }
+}
+
+hipError_t launch_normalize_cutoff(const float* x, float* y, size_t n, float mu, float sd, float c, hipStream_t s) {
+    if (!(c > 0.0f)) return launch_normalize(x, y, n, mu, sd, s);      // no cutoff: the bytes of launch_normalize
+    if (n == 0) return hipSuccess;
+    int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    hipLaunchKernelGGL(normalize_cutoff_kernel, dim3(blocks), dim3(256), 0, s, x, y, n, mu, sd, c);
+    return hipGetLastError();
+}
+
 // y[z][y][x] (dense) = x_view[z][y][x]*p[0] + p[1] with p on the device: the (x - mu)/std step of
 // Denoise._denoise (denoise.py:284) applied to a (strided) patch view before the network reads it.
 __global__ __launch_bounds__(256) void affine_dev_kernel(const float* __restrict__ x, int D, int H, int W,

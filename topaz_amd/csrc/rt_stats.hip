@@ -138,3 +138,13 @@ int tpz_normalize(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float st
     HIPCHK(ctx, e);
     return 0;
 }
+
+int tpz_normalize_cutoff(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float std, float cutoff, float* d_y) {
+    if (!ctx || !d_x || !d_y) return fail(ctx, "tpz_normalize_cutoff: bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    prof_begin(ctx, 2, 0);
+    hipError_t e = launch_normalize_cutoff(d_x, d_y, n, mean, std, cutoff, ctx->stream);
+    prof_end(ctx);
+    HIPCHK(ctx, e);
+    return 0;
+}

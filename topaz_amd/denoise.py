@@ -278,21 +278,29 @@ def denoise_image(mic: np.ndarray, models: List[Denoise], lowpass=1, cutoff=0, g
 
 def denoise_image_device(x: torch.Tensor, models: List[Denoise], patch_size: int = -1, padding: int = 0,
                          normalize: bool = False, lowpass: float = 1, deconvolve: bool = False,
-                         deconv_patch: int = 1) -> torch.Tensor:
-    """denoise_image (denoise.py:382-416) for the plain case -- no pixel cutoff, no Gaussian / inverse filter -- with the
-    micrograph staying on the device: population mean / std (the reference's numpy statistics, here a deterministic fp64
-    reduction on the GPU), (x - mu) / std, the networks' average, then either re-normalisation or std * y + mu.  The CLI path
-    spends no host pass over the 16.7 M pixels this way (the numpy version costs ~130 ms per 4096^2 micrograph, 7x the GPU
-    work of the network).  lowpass > 1 filters the raw micrograph first, deconvolve the normalised one before the networks
-    (the reference's order); with no model the pre-filtered image passes through (`-m none`)."""
+                         deconv_patch: int = 1, cutoff: float = 0, gaus: GaussianDenoise = None,
+                         inv_gaus: InvGaussianFilter = None) -> torch.Tensor:
+    """denoise_image (denoise.py:382-416) with the micrograph staying on the device: population mean / std (the reference's
+    numpy statistics, here a deterministic fp64 reduction on the GPU), (x - mu) / std, the networks' average, then either
+    re-normalisation or std * y + mu.  The CLI path spends no host pass over the 16.7 M pixels this way (the host passes of the
+    numpy version measured in DESIGN.md §14).  The options in the reference's order (:386-414): lowpass > 1 filters the raw
+    micrograph; cutoff > 0 zeroes the normalised pixels beyond +-cutoff in the normalisation launch itself
+    (tpz_normalize_cutoff); then exactly one filter of the normalised image -- gaus before inv_gaus before deconvolve, the
+    reference's if / elif / elif -- on the device tensor; with no model the pre-filtered image passes through (`-m none`)."""
     from . import runtime as rt
+    deconvolve = bool(deconvolve) and gaus is None and inv_gaus is None       # (the branch that runs)
     if deconvolve:
         deconv_tiles(*x.shape, deconv_patch)                # refused before anything runs
     if lowpass > 1:
         x = _lowpass(x, lowpass)
     mu, std = rt.mean_std(x, unbiased=False)
-    xn = rt.normalize(x, mu, std)              # (x - mu) / std as numpy rounds it; std == 0 -> inf / nan like upstream
-    if deconvolve:
+    # (x - mu) / std as numpy rounds it; std == 0 -> inf / nan like upstream
+    xn = rt.normalize_cutoff(x, mu, std, cutoff) if cutoff > 0 else rt.normalize(x, mu, std)
+    if gaus is not None:
+        xn = gaus(xn)
+    elif inv_gaus is not None:
+        xn = inv_gaus(xn)
+    elif deconvolve:
         xn = correct_spatial_covariance(xn, patch=deconv_patch)
     out = None if models else xn
     for model in models:
@@ -355,11 +363,18 @@ def _run_jobs(jobs: List[_Job], read, process, write, progress) -> list:
 def denoise_stack(path: str, output_path: str, models: List[Denoise], lowpass: float = 1, pixel_cutoff: float = 0,
                   gaus=None, inv_gaus=None, deconvolve: bool = True, deconv_patch: int = 1, patch_size: int = 1024,
                   padding: int = 500, normalize: bool = True, use_cuda: bool = True):
-    """every section of one MRC stack, written back as one stack with the input's header"""
+    """every section of one MRC stack, written back as one stack with the input's header.  On the device (runs_on_device) the
+    sections go through the ring of denoise_stream, each with its own statistics, and rank r of a multi-process launch takes
+    sections r, r + world, ... -- all ranks write the one output file (_denoise_stack_device); otherwise the host loop."""
     from . import mrc
     with open(path, 'rb') as f:
         stack, header, extended_header = mrc.parse(f.read())
     print('# denoising stack with shape:', stack.shape, file=sys.stderr)
+    models = models or []
+    if stack.dtype.kind in 'iuf' and runs_on_device(models, lowpass, pixel_cutoff, gaus, inv_gaus, deconvolve):
+        return _denoise_stack_device(stack, header, extended_header, output_path, models, patch_size, padding, normalize,
+                                     lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch, cutoff=pixel_cutoff,
+                                     gaus=gaus, inv_gaus=inv_gaus)
     out = np.zeros_like(stack)
     for k, section in enumerate(stack):
         out[k] = denoise_image(section, models, lowpass=lowpass, cutoff=pixel_cutoff, gaus=gaus, inv_gaus=inv_gaus,
@@ -389,13 +404,12 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
             for i in parallel.shard_indices(len(micrographs), rank, world)]
 
     models = models or []
-    # every pass over the pixels on the device unless a pixel cutoff or a Gaussian asks for the host path; `-m none` without
-    # a pre-filter keeps the host pass-through
-    on_device = (pixel_cutoff <= 0 and gaus is None and inv_gaus is None and all(m.dims == 2 for m in models) and
-                 (len(models) > 0 or lowpass > 1 or deconvolve))
-    if on_device:
+    # every pass over the pixels on the device, whatever the options; a 3-D model, or `-m none` without a pre-filter (a
+    # pass-through), keeps the host loop
+    if runs_on_device(models, lowpass, pixel_cutoff, gaus, inv_gaus, deconvolve):
         return _denoise_stream_device(jobs, models, patch_size, padding, normalize, len(micrographs), return_images,
-                                      lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch)
+                                      lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch, cutoff=pixel_cutoff,
+                                      gaus=gaus, inv_gaus=inv_gaus)
 
     def read(job):
         loaded = load_image(job.src, make_image=False)
@@ -415,24 +429,103 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
     return out
 
 
+def runs_on_device(models, lowpass: float = 1, pixel_cutoff: float = 0, gaus=None, inv_gaus=None,
+                   deconvolve: bool = False) -> bool:
+    """whether denoise_stream / denoise_stack keep the images on the device: every model is 2-D and there is something to do --
+    a model, or any pre-filter.  A 3-D model, or `-m none` with no filter (a pass-through), takes the host loop."""
+    return all(m.dims == 2 for m in models) and bool(len(models) > 0 or lowpass > 1 or deconvolve or pixel_cutoff > 0 or
+                                                     gaus is not None or inv_gaus is not None)
+
+
+# sections of a stack below this many bytes run one by one on the calling thread instead of through the ring
+RING_MIN_BYTES = 1 << 20
+
+
+def stack_section_offset(k: int, ny: int, nx: int, extended_bytes: int) -> int:
+    """byte of section k in an MRC stack as mrc.write lays it out: the 1024-byte header, the extended header, float32 sections"""
+    return 1024 + extended_bytes + 4 * k * ny * nx
+
+
 def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: int, padding: int, normalize: bool, total: int,
-                           return_images: bool = False, lowpass: float = 1, deconvolve: bool = False,
-                           deconv_patch: int = 1) -> list:
-    """the plain `topaz denoise` loop with every pass over the pixels on the device: a reader thread decodes micrograph i+1
-    into pinned memory and queues its upload (extract.ImageFeed), the GPU denoises micrograph i (denoise_image_device), its
-    result is copied into a pinned slot by the copy stream and a writer thread writes micrograph i-1 from there."""
+                           return_images: bool = False, **options) -> list:
+    """the `topaz denoise` loop with every pass over the pixels on the device (_device_ring); options: the keyword arguments of
+    denoise_image_device (lowpass, deconvolve, deconv_patch, cutoff, gaus, inv_gaus)"""
+    from .utils.image import save_image
+    results = [job.dst for job in jobs]
+
+    def emit(n, path, host, header, extended):
+        save_image(host, jobs[n].dst, header=header, extended_header=extended)
+        if return_images:
+            results[n] = np.array(host, copy=True)
+
+    _device_ring([job.src for job in jobs], models, lambda x: denoise_image_device(x, models, patch_size, padding, normalize,
+                                                                                   **options), emit, total)
+    return results
+
+
+def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_path: str, models: List[Denoise], patch_size: int,
+                          padding: int, normalize: bool, **options) -> np.ndarray:
+    """`topaz denoise --stack` through the ring of the stream: section k+1 uploads and section k-1 leaves under the kernels of
+    section k, each section with its own statistics (sections below RING_MIN_BYTES run one by one on the calling thread
+    instead, through the same functions).  The writer thread casts a section to the stack's dtype (what the host
+    loop's np.zeros_like(stack) does to an integer stack) and puts its float32 form at its byte of the output file (os.pwrite).
+    Rank r of a multi-process launch takes sections r, r + world, ...; rank 0 lays down the header, and a barrier makes the file
+    whole before any rank returns.  Returns the full stack (one process) or this rank's sections in a zero array."""
+    from . import mrc, parallel
+    rank, local_rank, world = parallel.init_from_env()
+    extended_header = extended_header or b''
+    sections = stack if stack.ndim == 3 else stack[None]          # (mrc.parse squeezes a one-section stack)
+    nz, ny, nx = sections.shape
+    mine = parallel.shard_indices(nz, rank, world)
+    out = np.zeros_like(sections)
+    print(f'# rank {rank} of {world}: stack sections {mine} of {nz}, writing to {output_path}', file=sys.stderr, flush=True)
+    fd = os.open(output_path, os.O_WRONLY | os.O_CREAT, 0o666)     # every rank opens the one file, none empties it
+    try:
+        if rank == 0:
+            # (the header mrc.write gives a stack written with the input's header; the length fixed up front cuts off what a
+            # longer file of an earlier run would leave behind)
+            os.pwrite(fd, mrc.header_struct.pack(*list(header._replace(mode=2))) + extended_header, 0)
+            os.ftruncate(fd, stack_section_offset(nz, ny, nx, len(extended_header)))
+
+        def emit(n, k, host, _header, _extended):
+            out[k] = host                                       # the cast to the stack's dtype (truncation for integers)
+            view = memoryview(np.ascontiguousarray(out[k], dtype=np.float32).reshape(-1)).cast('B')
+            at, done = stack_section_offset(k, ny, nx, len(extended_header)), 0
+            while done < len(view):
+                done += os.pwrite(fd, view[done:], at + done)
+
+        def process(x):
+            return denoise_image_device(x, models, patch_size, padding, normalize, **options)
+
+        if 4 * ny * nx >= RING_MIN_BYTES:
+            _device_ring([(k, sections[k], None, None) for k in mine], models, process, emit, nz)
+        else:
+            # small sections: the copies the ring would hide are shorter than its hand-offs between threads (DESIGN.md §14)
+            ctx = models[0].model.device_model.ctx if models else rt.get_context()
+            for n, k in enumerate(mine):
+                emit(n, k, process(rt.as_device_f32(np.array(sections[k], dtype=np.float32), ctx)).cpu().numpy(), None, None)
+                print(f'# {n + 1} of {nz} completed.', file=sys.stderr, end='\r')
+            print('', file=sys.stderr)
+    finally:
+        os.close(fd)
+    if world > 1:
+        parallel.barrier(parallel.collective_device(local_rank))   # every rank's sections are in the file
+    return out.reshape(stack.shape)
+
+
+def _device_ring(items: list, models: List[Denoise], process, emit, total: int) -> None:
+    """The device-resident loop shared by the stream and the stack.  items: file paths, or (key, array, header, extended
+    header) for images already in memory.  A reader thread decodes image i+1 into pinned memory and queues its upload
+    (extract.ImageFeed), the GPU runs process(device tensor) -> device tensor on image i, the result is copied into a pinned
+    slot by the copy stream, and a writer thread calls emit(i, path or key, pinned host array, header, extended header) for
+    image i-1 from there."""
     import queue
     import threading
     from . import runtime as rt
     from .extract import ImageFeed
-    from .utils.image import save_image
-    results = []
-    if not jobs:
-        return results
+    if not items:
+        return
     ctx = models[0].model.device_model.ctx if models else rt.get_context()
-    by_src = {}
-    for job in jobs:
-        by_src.setdefault(job.src, []).append(job)
     out_stage, out_bytes, DEPTH = None, 0, 2
     free_slots: 'queue.Queue' = queue.Queue()
     todo: 'queue.Queue' = queue.Queue()
@@ -443,12 +536,10 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
             item = todo.get()
             if item is None:
                 return
-            stage, k, shape, dst, header, extended, index, _device_result = item      # (the tensor lives until its copy is done)
+            stage, k, shape, key, header, extended, index, _device_result = item      # (the tensor lives until its copy is done)
             try:
                 stage.wait(k)                                # the D2H of this slot has landed
-                save_image(stage.host_array(k, shape), dst, header=header, extended_header=extended)
-                if return_images:
-                    results[index] = np.array(stage.host_array(k, shape), copy=True)
+                emit(index, key, stage.host_array(k, shape), header, extended)
             except BaseException as e:                       # surfaces in the main thread
                 failed.append(e)
             finally:
@@ -458,10 +549,8 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
     th.start()
     retired = []
     try:
-        for n, (path, x, header, extended) in enumerate(ImageFeed([j.src for j in jobs], ctx, headers=True)):
-            job = by_src[path].pop(0)
-            y = denoise_image_device(x, models, patch_size, padding, normalize, lowpass=lowpass, deconvolve=deconvolve,
-                                     deconv_patch=deconv_patch)
+        for n, (key, x, header, extended) in enumerate(ImageFeed(items, ctx, headers=True)):
+            y = process(x)
             nbytes = y.numel() * 4
             if out_stage is None or nbytes > out_bytes:
                 # (a larger image: a new ring; the old one is closed once the writer has drained it)
@@ -477,8 +566,7 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
             if failed:
                 raise failed[0]
             stage.download(k, y)
-            results.append(job.dst)
-            todo.put((stage, k, tuple(y.shape), job.dst, header, extended, n, y))
+            todo.put((stage, k, tuple(y.shape), key, header, extended, n, y))
             print(f'# {n + 1} of {total} completed.', file=sys.stderr, end='\r')
     finally:
         todo.put(None)
@@ -488,7 +576,6 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
     if failed:
         raise failed[0]
     print('', file=sys.stderr)
-    return results
 
 
 def _tomogram_io():

@@ -213,7 +213,9 @@ class ImageFeed:
     DEPTH = 3
 
     def __init__(self, paths: Sequence[str], ctx: 'rt.Context', headers: bool = False):
-        """headers=True: items are (path, tensor, MRC header or None, extended header or None)"""
+        """headers=True: items are (path, tensor, MRC header or None, extended header or None).  An entry of `paths` that is not
+        a string is an image already in memory, (key, array, header, extended header): it takes the same ring, its key in the
+        place of the path."""
         self.paths, self.ctx, self.headers = list(paths), ctx, headers
         self.stage: Optional[rt.Stage] = None
         self.slot_bytes = 0
@@ -286,13 +288,17 @@ class ImageFeed:
                 header = extended = None
                 try:
                     # an MRC file is decoded straight into pinned memory (float32: read INTO it); anything else is loaded and
-                    # converted into it
-                    got = mrc.read_into(path, pinned) if os.path.splitext(path)[1] == '.mrc' else None
+                    # converted into it; so is an image the caller already holds (a section of a stack)
+                    in_memory = not isinstance(path, str)
+                    if in_memory:
+                        path, image, header, extended = path
+                    got = mrc.read_into(path, pinned) if not in_memory and os.path.splitext(path)[1] == '.mrc' else None
                     if got is not None:
                         host, header, extended = got
                     else:
-                        loaded = load_image(path, make_image=False)
-                        image, header, extended = loaded if isinstance(loaded, tuple) else (loaded, None, None)
+                        if not in_memory:
+                            loaded = load_image(path, make_image=False)
+                            image, header, extended = loaded if isinstance(loaded, tuple) else (loaded, None, None)
                         image = np.asarray(image)
                         host = pinned(image.shape)
                         np.copyto(host, image, casting='unsafe')

@@ -754,6 +754,18 @@ def normalize(x: torch.Tensor, mean: float, std: float, ctx: Optional[Context] =
     return y
 
 
+def normalize_cutoff(x: torch.Tensor, mean: float, std: float, cutoff: float, ctx: Optional[Context] = None) -> torch.Tensor:
+    """normalize() with denoise_image's pixel cutoff fused (tpz_normalize_cutoff): v = (x - mean) / std, then 0 where
+    v < -cutoff or v > cutoff, compared in fp32; NaN passes, +-inf is zeroed; cutoff <= 0 is normalize()"""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = as_device_f32(x, ctx)
+    y = torch.empty_like(x)
+    check(ctx.lib.tpz_normalize_cutoff(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), float(cutoff), _ptr(y)),
+          ctx.handle)
+    return y
+
+
 def filter_2d(x: torch.Tensor, w, bias: float = 0.0, ctx: Optional[Context] = None) -> torch.Tensor:
     ctx = ctx or get_context()
     ctx.bind_current_stream()
