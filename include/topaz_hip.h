@@ -173,6 +173,13 @@ int tpz_normalize(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float st
  * array and a Python float).  NaN passes through unchanged, +-inf (std == 0) is zeroed.  cutoff <= 0: no cutoff, the bytes of
  * tpz_normalize.  Asynchronous; one launch. */
 int tpz_normalize_cutoff(tpz_ctx* ctx, const float* d_x, size_t n, float mean, float std, float cutoff, float* d_y);
+/* d_out[i] = (float)d_raw[i] for n pixels in the type an MRC file of mode mrc_mode stores them in: 0 int8, 1 int16, 6 uint16,
+ * 12 float16 (any other mode is an error).  All four conversions are exact: the result is the bits of numpy's
+ * astype(np.float32), for float16 over all 65 536 patterns (subnormals become normal fp32 values, zeros and infinities keep
+ * their sign, a NaN stays a NaN) whatever the float mode of the device, because it is done in integer arithmetic.  d_raw must be
+ * 16-byte aligned (one 16-byte load per lane), d_out 4-byte (16-byte for the vector stores; otherwise a slower scalar loop).
+ * n == 0 does nothing.  The buffers must not overlap.  Asynchronous; one launch. */
+int tpz_decode(tpz_ctx* ctx, const void* d_raw, int mrc_mode, size_t n, float* d_out);
 /* 1->1 channel 2-D filter with zero "same" padding: GaussianDenoise / InvGaussianFilter /
  * AffineFilter.forward (topaz/filters.py:28-96).  h_w is the [k][k] kernel on the host. */
 int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_w, int k, float bias,
@@ -245,6 +252,16 @@ int tpz_stage_acquire(tpz_stage* st, int slot);
 int tpz_stage_release(tpz_stage* st, int slot);
 int tpz_stage_d2h(tpz_stage* st, int slot, const void* d_src, size_t bytes);
 int tpz_stage_wait(tpz_stage* st, int slot);
+/* tpz_stage_h2d for an image whose pixels lie in the slot's pinned buffer in the type the file stores them in (mrc_mode 0, 1, 6
+ * or 12: see tpz_decode): the n * itemsize stored bytes are copied to a raw region of the slot's device buffer, BEHIND the fp32
+ * image (at the next multiple of 256 bytes after 4 * n), decoded into the start of the slot by tpz_decode's kernel on the copy
+ * stream, and only then is the slot's copy event recorded.  tpz_stage_acquire / tpz_stage_device_ptr and every consumer see
+ * what they see after tpz_stage_h2d -- n fp32 pixels at the start of the slot -- while a quarter or half of the bytes crossed
+ * the bus and the host converted nothing.  The slot must hold tpz_stage_decode_bytes(mrc_mode, n) bytes (4 * n rounded up to
+ * 256, plus the stored bytes rounded up to 256; 0 for a mode that is not decoded).  The launch is not counted by
+ * tpz_prof_launches (it is not on the ctx stream). */
+size_t tpz_stage_decode_bytes(int mrc_mode, size_t n);
+int tpz_stage_h2d_decode(tpz_stage* st, int slot, int mrc_mode, size_t n);
 /* Host-pointer forms of the three calls of the path (synchronous; plain pageable or pinned memory), the signatures
  * SURVEY.md 8(b) sketches: model(x) on a numpy image (extract.py:247-249), Denoise.denoise (denoise.py:327-332),
  * non_maximum_suppression (algorithms.py:25-63).  Each stages through an internal ring owned by the ctx. */

@@ -89,6 +89,9 @@ _SIGNATURES = {
     'tpz_stage_release': (C.c_int, [_P, C.c_int]),
     'tpz_stage_d2h': (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     'tpz_stage_wait': (C.c_int, [_P, C.c_int]),
+    'tpz_decode': (C.c_int, [_P, _P, C.c_int, C.c_size_t, _P]),
+    'tpz_stage_decode_bytes': (C.c_size_t, [C.c_int, C.c_size_t]),
+    'tpz_stage_h2d_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t]),
     'tpz_score_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     'tpz_denoise_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'tpz_nms_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int, C.POINTER(C.c_int)]),

@@ -25,6 +25,25 @@ hipError_t launch_normalize(const float* x, float* y, size_t n, float mu, float 
 hipError_t launch_normalize_cutoff(const float* x, float* y, size_t n, float mu, float sd, float c, hipStream_t s);
 hipError_t launch_affine_dev(const float* x, int D, int H, int W, long long ps, int pitch, const float* d_p, float* y,
                              hipStream_t s);
+
+// Stored MRC pixel types -> fp32 (decode_kernel).  Bytes per pixel of the real scalar modes the library decodes on the device
+// (0 int8, 1 int16, 6 uint16, 12 float16); 0 for every other mode.
+static inline size_t stored_itemsize(int mrc_mode) {
+    return mrc_mode == 0 ? 1 : (mrc_mode == 1 || mrc_mode == 6 || mrc_mode == 12) ? 2 : 0;
+}
+// The fp32 bits of a binary16 value, by integer operations only: what numpy's astype(float32) gives for all 65 536 patterns --
+// the 2 046 subnormals become the normal fp32 value m * 2^-24 (an exact int -> float conversion and an exact scaling by a power
+// of two, so no float mode of the device, denormal flushing included, can touch it), zeros and infinities keep their sign, a NaN
+// keeps sign and payload.
+__host__ __device__ static inline unsigned f16_bits_to_f32_bits(unsigned h) {
+    const unsigned sign = (h & 0x8000u) << 16, em = h & 0x7fffu;
+    if (em >= 0x7c00u) return sign | 0x7f800000u | ((em & 0x3ffu) << 13);      // inf / NaN
+    if (em >= 0x0400u) return sign | ((em << 13) + (112u << 23));              // normal: exponent rebias 15 -> 127
+    return sign | __builtin_bit_cast(unsigned, (float)(int)em * 0x1p-24f);     // zero / subnormal
+}
+// out[i] = (float)raw[i] for n pixels of MRC mode 0 / 1 / 6 / 12 (any other mode: hipErrorInvalidValue).  raw must be 16-byte
+// aligned; out 4-byte (16-byte for the vector body, otherwise every pixel takes the scalar loop).  One launch; n == 0: none.
+hipError_t launch_decode(const void* raw, int mrc_mode, size_t n, float* out, hipStream_t s);
 hipError_t launch_transpose(const float* in, float* out, int R, int Cc, hipStream_t s);
 hipError_t launch_maxpool2_split(const void* in, void* out, int C, int D, int H, int W, int dims, hipStream_t s);
 hipError_t launch_maxpoolz_split(const float* in, float* out, int C, int D, int H, int W, hipStream_t s);   // z pairs only (split cells)

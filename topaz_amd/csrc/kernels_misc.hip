@@ -453,6 +453,62 @@ hipError_t launch_normalize_cutoff(const float* x, float* y, size_t n, float mu,
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// stored MRC pixel types -> fp32: int8 (mode 0), int16 (1), uint16 (6), float16 (12).  Every conversion is exact, so the image
+// is the bits of numpy's astype(float32).  Each lane takes one 16-byte load of stored pixels (16 int8 or 8 two-byte pixels) and
+// writes them as four or two 16-byte stores; the n % 16 (n % 8) pixels behind the last whole 16 bytes go one by one.  Both
+// loops stride over the grid.  No LDS, no atomics: the pass is bound by the 4n bytes it writes.
+// ------------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ float stored_to_f32(unsigned bits) {       // bits: one stored pixel, zero-extended
+    if (MODE == 0) return (float)(int)(signed char)bits;
+    if (MODE == 1) return (float)(int)(short)bits;
+    if (MODE == 6) return (float)bits;
+    return __uint_as_float(f16_bits_to_f32_bits(bits));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void decode_kernel(const void* __restrict__ raw, float* __restrict__ out, size_t n_vec,
+                                                     size_t n) {
+    constexpr int EPL = MODE == 0 ? 16 : 8;                           // pixels per 16-byte load
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t c = t; c < n_vec; c += stride) {
+        const uint4 v = ((const uint4*)raw)[c];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+        float4* o = (float4*)(out + c * EPL);
+        if (MODE == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                o[k] = make_float4(stored_to_f32<MODE>(w[k] & 0xffu), stored_to_f32<MODE>((w[k] >> 8) & 0xffu),
+                                   stored_to_f32<MODE>((w[k] >> 16) & 0xffu), stored_to_f32<MODE>(w[k] >> 24));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                o[k] = make_float4(stored_to_f32<MODE>(w[2 * k] & 0xffffu), stored_to_f32<MODE>(w[2 * k] >> 16),
+                                   stored_to_f32<MODE>(w[2 * k + 1] & 0xffffu), stored_to_f32<MODE>(w[2 * k + 1] >> 16));
+        }
+    }
+    for (size_t i = n_vec * EPL + t; i < n; i += stride)
+        out[i] = stored_to_f32<MODE>(MODE == 0 ? (unsigned)((const unsigned char*)raw)[i] : (unsigned)((const unsigned short*)raw)[i]);
+}
+
+hipError_t launch_decode(const void* raw, int mrc_mode, size_t n, float* out, hipStream_t s) {
+    const size_t item = stored_itemsize(mrc_mode);
+    if (item == 0 || ((uintptr_t)raw & 15) || ((uintptr_t)out & 3)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    // (an `out` that is only 4-byte aligned cannot take the 16-byte stores: every pixel goes through the scalar loop)
+    const size_t n_vec = ((uintptr_t)out & 15) ? 0 : n / (16 / item);
+    const size_t work = std::max(n_vec, n - n_vec * (16 / item));     // threads the longer of the two loops can use
+    const int blocks = (int)std::min<size_t>((work + 255) / 256, 8192);
+    switch (mrc_mode) {
+        case 0: hipLaunchKernelGGL(decode_kernel<0>, dim3(blocks), dim3(256), 0, s, raw, out, n_vec, n); break;
+        case 1: hipLaunchKernelGGL(decode_kernel<1>, dim3(blocks), dim3(256), 0, s, raw, out, n_vec, n); break;
+        case 6: hipLaunchKernelGGL(decode_kernel<6>, dim3(blocks), dim3(256), 0, s, raw, out, n_vec, n); break;
+        default: hipLaunchKernelGGL(decode_kernel<12>, dim3(blocks), dim3(256), 0, s, raw, out, n_vec, n); break;
+    }
+    return hipGetLastError();
+}
+
 // y[z][y][x] (dense) = x_view[z][y][x]*p[0] + p[1] with p on the device: the (x - mu)/std step of
 // Denoise._denoise (denoise.py:284) applied to a (strided) patch view before the network reads it.
 __global__ __launch_bounds__(256) void affine_dev_kernel(const float* __restrict__ x, int D, int H, int W,

@@ -23,6 +23,9 @@ tpz_stage::Slot* stage_slot(tpz_stage* st, int slot) {
     return (st && slot >= 0 && slot < (int)st->slots.size()) ? &st->slots[slot] : nullptr;
 }
 
+// tpz_stage_h2d_decode: the stored pixels of an n-pixel image lie behind its fp32 form, at the next multiple of 256 bytes
+size_t stage_raw_offset(size_t n) { return (4 * n + 255) & ~(size_t)255; }
+
 // host-pointer entry points: two slots of the ctx's own ring (input, output), grown on demand
 int io_stage(tpz_ctx* ctx, size_t bytes, tpz_stage** out) {
     if (ctx->io_stage && ctx->io_stage->slot_bytes < bytes) { tpz_stage_free(ctx->io_stage); ctx->io_stage = nullptr; }
@@ -85,6 +88,32 @@ int tpz_stage_h2d(tpz_stage* st, int slot, const void* h_src, size_t bytes) {
     }
     HIPCHK(ctx, hipStreamWaitEvent(st->copy, sl->released, 0));      // kernels of the slot's previous use are done
     HIPCHK(ctx, hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, st->copy));
+    HIPCHK(ctx, hipEventRecord(sl->ready, st->copy));
+    return 0;
+}
+size_t tpz_stage_decode_bytes(int mrc_mode, size_t n) {
+    const size_t item = stored_itemsize(mrc_mode);
+    if (item == 0 || n > ((size_t)1 << 60)) return 0;
+    return stage_raw_offset(n) + ((n * item + 255) & ~(size_t)255);
+}
+int tpz_stage_h2d_decode(tpz_stage* st, int slot, int mrc_mode, size_t n) {
+    auto* sl = stage_slot(st, slot);
+    tpz_ctx* ctx = st ? st->ctx : nullptr;
+    if (!sl) return fail(ctx, "tpz_stage_h2d_decode: bad slot");
+    const size_t item = stored_itemsize(mrc_mode), need = tpz_stage_decode_bytes(mrc_mode, n);
+    if (item == 0) return fail(ctx, "tpz_stage_h2d_decode: MRC mode %d is not one of the stored real types 0, 1, 6, 12", mrc_mode);
+    if (n > ((size_t)1 << 60) || need > st->slot_bytes)
+        return fail(ctx, "tpz_stage_h2d_decode: %zu pixels of mode %d need a slot of %zu bytes, this ring has %zu", n, mrc_mode,
+                    need, st->slot_bytes);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // stored pixels behind the fp32 image they decode into; the decode runs on the copy stream, between the copy and the event,
+    // so `ready` means what it means after tpz_stage_h2d: an fp32 image at the start of the slot
+    void* d_raw = (char*)sl->d + stage_raw_offset(n);
+    HIPCHK(ctx, hipStreamWaitEvent(st->copy, sl->released, 0));      // kernels of the slot's previous use are done
+    if (n) {
+        HIPCHK(ctx, hipMemcpyAsync(d_raw, sl->h, n * item, hipMemcpyHostToDevice, st->copy));
+        HIPCHK(ctx, launch_decode(d_raw, mrc_mode, n, (float*)sl->d, st->copy));
+    }
     HIPCHK(ctx, hipEventRecord(sl->ready, st->copy));
     return 0;
 }

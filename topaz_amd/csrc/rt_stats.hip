@@ -1,4 +1,4 @@
-// Statistics and elementwise entry points: mean / std, GMM fit (topaz normalize), affine, normalise.
+// Statistics and elementwise entry points: mean / std, GMM fit (topaz normalize), affine, normalise, stored-type decode.
 #include <cstddef>
 #include "rt_internal.h"
 
@@ -146,5 +146,18 @@ int tpz_normalize_cutoff(tpz_ctx* ctx, const float* d_x, size_t n, float mean, f
     hipError_t e = launch_normalize_cutoff(d_x, d_y, n, mean, std, cutoff, ctx->stream);
     prof_end(ctx);
     HIPCHK(ctx, e);
+    return 0;
+}
+
+int tpz_decode(tpz_ctx* ctx, const void* d_raw, int mrc_mode, size_t n, float* d_out) {
+    if (!ctx || !d_raw || !d_out) return fail(ctx, "tpz_decode: bad arguments");
+    const size_t item = stored_itemsize(mrc_mode);
+    if (item == 0) return fail(ctx, "tpz_decode: MRC mode %d is not one of the stored real types 0, 1, 6, 12", mrc_mode);
+    if (n == 0) return 0;
+    if (((uintptr_t)d_raw & 15) || ((uintptr_t)d_out & 3))
+        return fail(ctx, "tpz_decode: d_raw must be 16-byte aligned (and d_out 4-byte)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, enqueue(ctx, 2, 0.0, nullptr, (double)n * (item + 4),
+                        [=](hipStream_t st) { return launch_decode(d_raw, mrc_mode, n, d_out, st); }));
     return 0;
 }

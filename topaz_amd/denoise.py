@@ -122,6 +122,8 @@ class Denoise3D(Denoise):
         if verbose:
             print(f'# [{volume_num}/{total_volumes}] 100%', file=sys.stderr, end='\r')
             print(' ' * 100, file=sys.stderr, end='\r')
+        if torch.is_tensor(tomo) and tomo.is_cuda:                # (a volume decoded on the device: _tomogram_io)
+            return y.cpu().numpy()
         return y.cpu().numpy().astype(np.asarray(tomo).dtype, copy=False)
 
 
@@ -582,6 +584,11 @@ def _tomogram_io():
     from . import mrc
 
     def read(job):
+        # an int8 / int16 / uint16 / float16 volume stays in its stored type (one read INTO the array, no host pass over the
+        # voxels): _tomogram_device sends it up as stored and tpz_decode makes the float32 volume there
+        got = mrc.read_stored_into(job.src, lambda shape, dtype: np.empty(shape, dtype=dtype))
+        if got is not None:
+            return got
         with open(job.src, 'rb') as f:
             tomo, header, extended = mrc.parse(f.read())
         return tomo.astype(np.float32), header, extended
@@ -594,17 +601,36 @@ def _tomogram_io():
     return read, write
 
 
+def _tomogram_device(model: 'Denoise3D', tomo: np.ndarray, pool) -> tuple:
+    """(what Denoise3D.denoise takes, the float32 volume the drivers return) for a volume as _tomogram_io read it.  A stored
+    type is decoded on the device (runtime.decode_stored); the float32 host copy callers of the drivers have always been handed
+    is made by a thread of `pool` under the denoising -- a future, resolved when the driver returns."""
+    from . import mrc
+    if tomo.dtype not in mrc.STORED_MODES:
+        return tomo, tomo
+    return rt.decode_stored(tomo, model.model.device_model.ctx), pool.submit(tomo.astype, np.float32)
+
+
+def _resolved(volume):
+    return volume if isinstance(volume, np.ndarray) else volume.result()
+
+
 def denoise_tomogram(path: str, model: Denoise3D, outdir: str = None, suffix: str = '', patch_size: int = 96,
                      padding: int = 48, volume_num: int = 1, total_volumes: int = 1, gaus=None, verbose: bool = True):
     """one tomogram; returns the INPUT volume, Gaussian-filtered when `gaus` is given -- what the reference returns
     (it filters `tomo`, writes `denoised`: denoise.py:509,528-530)"""
     read, write = _tomogram_io()
     job = _Job(0, path, _output_path(path, outdir, suffix, os.path.splitext(path)[1]))
+    from concurrent.futures import ThreadPoolExecutor
     item = read(job)
-    denoised = model.denoise(item[0], patch_size=patch_size, padding=padding, batch_size=1, volume_num=volume_num,
-                             total_volumes=total_volumes, verbose=verbose)
-    write(job, item, denoised)
-    return gaus.apply(item[0]) if gaus is not None else item[0]
+    with ThreadPoolExecutor(1, 'tpz-f32') as pool:
+        x, volume = _tomogram_device(model, item[0], pool)
+        denoised = model.denoise(x, patch_size=patch_size, padding=padding, batch_size=1, volume_num=volume_num,
+                                 total_volumes=total_volumes, verbose=verbose)
+        del x
+        write(job, item, denoised)
+        volume = _resolved(volume)
+    return gaus.apply(volume) if gaus is not None else volume
 
 
 def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: str, suffix: str = '', gaus: float = None,
@@ -630,9 +656,13 @@ def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: s
     jobs = [_Job(i, volumes[i], _output_path(volumes[i], output_path, suffix, os.path.splitext(volumes[i])[1])) for i in mine]
     inputs = []          # upstream returns the list of (unfiltered) input volumes; kept for the same return value
 
+    from concurrent.futures import ThreadPoolExecutor
+    pool = ThreadPoolExecutor(1, 'tpz-f32')
+
     def process(job, item):
-        inputs.append(item[0])
-        return model.denoise(item[0], patch_size=patch_size, padding=padding, batch_size=1, volume_num=job.index + 1,
+        x, volume = _tomogram_device(model, item[0], pool)
+        inputs.append(volume)
+        return model.denoise(x, patch_size=patch_size, padding=padding, batch_size=1, volume_num=job.index + 1,
                              total_volumes=total, verbose=verbose and rank == 0, across_ranks=by_tiles)
 
     if by_tiles:
@@ -642,6 +672,10 @@ def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: s
             if denoised is not None:
                 plain_write(job, item, denoised)
 
-    _run_jobs(jobs, read, process, write, lambda n: print(f'# {n} of {total} tomograms denoised.', file=sys.stderr, end='\r'))
+    try:
+        _run_jobs(jobs, read, process, write, lambda n: print(f'# {n} of {total} tomograms denoised.', file=sys.stderr, end='\r'))
+        inputs = [_resolved(v) for v in inputs]
+    finally:
+        pool.shutdown()
     print('', file=sys.stderr)
     return inputs

@@ -205,10 +205,11 @@ def find_opt_radius(targets, target_scores, threshold, lo=0, hi=200, step=10, ma
 # scoring
 # ---------------------------------------------------------------------------------------------------------------------
 class ImageFeed:
-    """Iterate (path, device tensor [H, W] or [D, H, W]) with the NEXT micrograph's disk read, fp32 conversion and H2D
-    copy running under the consumer's work on the current one.  A reader thread decodes into the pinned buffer of a
-    free staging slot and queues the copy; the consumer acquires the slot on its stream, uses the tensor, and the slot is
-    released (for re-use two images later) when the consumer asks for the next item."""
+    """Iterate (path, device tensor [H, W] or [D, H, W]) with the NEXT micrograph's disk read, H2D copy and fp32 conversion
+    running under the consumer's work on the current one.  A reader thread reads into the pinned buffer of a free staging
+    slot and queues the copy; the consumer acquires the slot on its stream, uses the tensor, and the slot is released (for
+    re-use two images later) when the consumer asks for the next item.  Pixels stored as int8, int16, uint16 or float16 cross
+    to the device as stored and become fp32 there, on the copy stream; the tensor yielded is fp32 either way."""
 
     DEPTH = 3
 
@@ -224,6 +225,7 @@ class ImageFeed:
         self.thread = threading.Thread(target=self._reader, daemon=True)
         self._retired: List['rt.Stage'] = []      # outgrown rings: closed by the consumer when the feed ends
         self._stop = threading.Event()           # the consumer left (done, or an exception): the reader must not block
+        self.uploaded_bytes = 0                  # pixel bytes queued host -> device so far (the reader thread counts them)
 
     def _ensure_stage(self, nbytes: int) -> None:
         # (called from the reader thread before any slot of a new, larger ring is handed out)
@@ -265,9 +267,12 @@ class ImageFeed:
 
             held = []
 
-            def pinned(shape):
-                """the pinned buffer of a free staging slot for an image of that shape (the ring grows when it must)"""
-                nbytes = int(np.prod(shape)) * 4
+            def pinned(shape, dtype=np.float32):
+                """the pinned buffer of a free staging slot for an image of that shape (the ring grows when it must).  A dtype
+                the device decodes (mrc.STORED_MODES): the slot holds the fp32 image and, behind it, the stored pixels"""
+                n = int(np.prod(shape))
+                mode = mrc.STORED_MODES.get(np.dtype(dtype))
+                nbytes = n * 4 if mode is None else rt.Stage.decode_bytes(self.ctx, mode, n)
                 if self.stage is None or nbytes > self.slot_bytes:
                     # wait until every slot of the old ring came back, then grow
                     if self.stage is not None:
@@ -281,18 +286,19 @@ class ImageFeed:
                 # the slot's previous upload may still be queued (a consumer that only enqueues runs ahead of the copy
                 # stream): the pinned buffer is refilled only after that copy has read it
                 slot[0].wait(slot[1])
-                held[:] = [slot, nbytes]
-                return slot[0].host_array(slot[1], shape)
+                held[:] = [slot, n, mode]
+                return slot[0].host_array(slot[1], shape, np.float32 if mode is None else dtype)
 
             for path in self.paths:
                 header = extended = None
                 try:
-                    # an MRC file is decoded straight into pinned memory (float32: read INTO it); anything else is loaded and
-                    # converted into it; so is an image the caller already holds (a section of a stack)
+                    # an MRC file is read straight into pinned memory IN THE TYPE IT STORES (float32, or int8 / int16 / uint16 /
+                    # float16, which the device decodes: Stage.upload_decode); anything else is loaded and converted into it; so
+                    # is an image the caller already holds (a section of a stack), which keeps a stored type of those four too
                     in_memory = not isinstance(path, str)
                     if in_memory:
                         path, image, header, extended = path
-                    got = mrc.read_into(path, pinned) if not in_memory and os.path.splitext(path)[1] == '.mrc' else None
+                    got = mrc.read_stored_into(path, pinned) if not in_memory and os.path.splitext(path)[1] == '.mrc' else None
                     if got is not None:
                         host, header, extended = got
                     else:
@@ -300,12 +306,16 @@ class ImageFeed:
                             loaded = load_image(path, make_image=False)
                             image, header, extended = loaded if isinstance(loaded, tuple) else (loaded, None, None)
                         image = np.asarray(image)
-                        host = pinned(image.shape)
+                        host = pinned(image.shape, image.dtype if image.dtype in mrc.STORED_MODES else np.float32)
                         np.copyto(host, image, casting='unsafe')
                 except _Left:
                     return
-                (stage, k), nbytes = held
-                stage.upload(k, nbytes)
+                (stage, k), n, mode = held
+                if mode is None:
+                    stage.upload(k, 4 * n)
+                else:
+                    stage.upload_decode(k, mode, n)
+                self.uploaded_bytes += n * host.dtype.itemsize
                 if not self._put_ready((path, stage, k, host.shape, header, extended)):
                     return
             self._put_ready(None)

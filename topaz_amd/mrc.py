@@ -87,6 +87,34 @@ def read_into(path: str, alloc):
     return out, header, extended_header
 
 
+# the real scalar modes other than float32: pixels the device decodes (tpz_decode), keyed by their (native) dtype
+STORED_MODES = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.uint16): 6, np.dtype(np.float16): 12}
+
+
+def read_stored_into(path: str, alloc):
+    """read_into without the conversion: the pixels of an MRC file of mode 0, 1, 6 or 12 are read INTO the array
+    `alloc(shape, dtype)` returns, in the dtype the file stores them in (int8, int16, uint16, float16) -- one copy from the page
+    cache, a quarter or half of the float32 bytes, nothing converted on the host; tpz_decode makes float32 of them on the device.
+    A float32 file (mode 2) is read as read_into reads it.  Returns (array, header, extended header), or None for the vector
+    modes (3, 4, 16).  Byte-swapped files are not recognised (neither are they by `parse`)."""
+    with open(path, 'rb') as f:
+        header = parse_header(f.read(1024))
+        mode = get_mode_from_header(header)
+        if isinstance(mode, str) or np.dtype(mode).kind == 'c':
+            return None
+        extended_header = f.read(header.next)
+        dt = np.dtype(mode)
+        n = header.nz * header.ny * header.nx
+        shape = (header.ny, header.nx) if header.nz == 1 else (header.nz, header.ny, header.nx)
+        out = alloc(shape, dt)
+        got = f.readinto(out.reshape(-1).view(np.uint8))
+        if got != dt.itemsize * n:
+            if dt == np.float32:
+                raise ValueError(f'{path}: {got} bytes of image data, header says {4 * n}')
+            raise ValueError(f'{path}: {got // dt.itemsize} pixels, header says {n}')
+    return out, header, extended_header
+
+
 def make_header(shape, cella, cellb, mz=1, dtype=np.float32, order=(1, 2, 3), dmin=0, dmax=-1, dmean=-2, rms=-1,
                 exthd_size=0, ispg=0) -> MRCHeader:
     return MRCHeader(shape[2], shape[1], shape[0], get_mode_for_header(dtype), 0, 0, 0, 1, 1, mz,

@@ -233,6 +233,20 @@ class Stage:
         ptr = None if src is None else np.ascontiguousarray(src).ctypes.data_as(C.c_void_p)
         check(self.ctx.lib.tpz_stage_h2d(self.handle, slot, ptr, int(nbytes)), self.ctx.handle)
 
+    @staticmethod
+    def decode_bytes(ctx: Context, mode: int, n: int) -> int:
+        """bytes a slot needs for upload_decode of n pixels of MRC mode `mode`: the fp32 image plus, behind it, the stored pixels"""
+        need = int(ctx.lib.tpz_stage_decode_bytes(int(mode), int(n)))
+        if need == 0 and n:
+            raise _lib.TopazHipError(f'MRC mode {mode} is not a stored type the device decodes (0, 1, 6, 12)')
+        return need
+
+    def upload_decode(self, slot: int, mode: int, n: int) -> None:
+        """upload() for n pixels that lie in the slot's pinned buffer in their stored type (host_array(slot, shape, dtype) filled
+        them): n * itemsize bytes cross to the device and are decoded to fp32 at the start of the slot on the copy stream
+        (tpz_stage_h2d_decode); acquire() / device_tensor() as after upload()"""
+        check(self.ctx.lib.tpz_stage_h2d_decode(self.handle, slot, int(mode), int(n)), self.ctx.handle)
+
     def acquire(self, slot: int) -> None:
         self.ctx.bind_current_stream()
         check(self.ctx.lib.tpz_stage_acquire(self.handle, slot), self.ctx.handle)
@@ -751,6 +765,25 @@ def normalize(x: torch.Tensor, mean: float, std: float, ctx: Optional[Context] =
     x = as_device_f32(x, ctx)
     y = torch.empty_like(x)
     check(ctx.lib.tpz_normalize(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), _ptr(y)), ctx.handle)
+    return y
+
+
+def decode_stored(x: np.ndarray, ctx: Optional[Context] = None) -> torch.Tensor:
+    """a numpy array of int8 / int16 / uint16 / float16 pixels -> the fp32 device tensor numpy's astype(np.float32) would give,
+    bit for bit (tpz_decode).  The array goes up in its stored type: a quarter or half of the float32 bytes cross the bus and
+    the host converts nothing."""
+    from .mrc import STORED_MODES
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x = np.ascontiguousarray(x)
+    mode = STORED_MODES.get(x.dtype)
+    if mode is None:
+        raise _lib.TopazHipError(f'decode_stored: {x.dtype} is not a stored type the device decodes (int8, int16, uint16, '
+                                 'float16)')
+    raw = torch.from_numpy(x.reshape(-1).view(np.uint8)).to(ctx.torch_device())
+    y = torch.empty(x.shape, dtype=torch.float32, device=ctx.torch_device())
+    if x.size:
+        check(ctx.lib.tpz_decode(ctx.handle, _ptr(raw), mode, x.size, _ptr(y)), ctx.handle)
     return y
 
 
