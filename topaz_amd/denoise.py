@@ -12,10 +12,14 @@ correct_spatial_covariance (:129-172) and the 2-D lowpass (:174-197).  Both flag
 (DESIGN.md §9): lowpass as fp64 GEMMs with the projections onto the kept frequencies (tpz_lowpass_2d), the deconvolution
 as per-tile lag covariances (tpz_spatial_cov_2d), the host's float64 filter design and one per-tile filter over the
 whole image (tpz_tile_filter_2d).
+
+The device-resident drivers of 2-D images (`denoise`, `denoise --stack`) are streaming.stream_images around
+denoise_image_device: the feed, the pinned result ring and its writer thread live in streaming.py, not here.
 """
 from __future__ import annotations
 
 import functools
+import itertools
 import os
 import sys
 from typing import List, Optional, Union
@@ -24,6 +28,7 @@ import numpy as np
 import torch
 
 from . import runtime as rt
+from . import streaming
 from .denoising.models import DenoiseNet, load_model
 from .filters import AffineFilter, GaussianDenoise, InvGaussianFilter
 
@@ -455,7 +460,7 @@ def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: 
     from .utils.image import save_image
     results = [job.dst for job in jobs]
 
-    def emit(n, path, host, header, extended):
+    def emit(host, n, path, header, extended):
         save_image(host, jobs[n].dst, header=header, extended_header=extended)
         if return_images:
             results[n] = np.array(host, copy=True)
@@ -489,12 +494,10 @@ def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_pat
             os.pwrite(fd, mrc.header_struct.pack(*list(header._replace(mode=2))) + extended_header, 0)
             os.ftruncate(fd, stack_section_offset(nz, ny, nx, len(extended_header)))
 
-        def emit(n, k, host, _header, _extended):
+        def emit(host, n, k, _header, _extended):
             out[k] = host                                       # the cast to the stack's dtype (truncation for integers)
-            view = memoryview(np.ascontiguousarray(out[k], dtype=np.float32).reshape(-1)).cast('B')
-            at, done = stack_section_offset(k, ny, nx, len(extended_header)), 0
-            while done < len(view):
-                done += os.pwrite(fd, view[done:], at + done)
+            streaming.pwrite_all(fd, np.ascontiguousarray(out[k], dtype=np.float32),
+                                 stack_section_offset(k, ny, nx, len(extended_header)))
 
         def process(x):
             return denoise_image_device(x, models, patch_size, padding, normalize, **options)
@@ -505,7 +508,7 @@ def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_pat
             # small sections: the copies the ring would hide are shorter than its hand-offs between threads
             ctx = models[0].model.device_model.ctx if models else rt.get_context()
             for n, k in enumerate(mine):
-                emit(n, k, process(rt.as_device_f32(np.array(sections[k], dtype=np.float32), ctx)).cpu().numpy(), None, None)
+                emit(process(rt.as_device_f32(np.array(sections[k], dtype=np.float32), ctx)).cpu().numpy(), n, k, None, None)
                 print(f'# {n + 1} of {nz} completed.', file=sys.stderr, end='\r')
             print('', file=sys.stderr)
     finally:
@@ -516,67 +519,21 @@ def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_pat
 
 
 def _device_ring(items: list, models: List[Denoise], process, emit, total: int) -> None:
-    """The device-resident loop shared by the stream and the stack.  items: file paths, or (key, array, header, extended
-    header) for images already in memory.  A reader thread decodes image i+1 into pinned memory and queues its upload
-    (extract.ImageFeed), the GPU runs process(device tensor) -> device tensor on image i, the result is copied into a pinned
-    slot by the copy stream, and a writer thread calls emit(i, path or key, pinned host array, header, extended header) for
-    image i-1 from there."""
-    import queue
-    import threading
-    from . import runtime as rt
-    from .extract import ImageFeed
+    """The device-resident loop shared by the stream and the stack (streaming.stream_images).  items: file paths, or (key, array,
+    header, extended header) for images already in memory.  The GPU runs process(device tensor) -> device tensor on image i
+    while image i+1 is decoded and uploaded, and a writer thread calls emit(pinned host array, i, path or key, header, extended
+    header) for image i-1."""
     if not items:
         return
     ctx = models[0].model.device_model.ctx if models else rt.get_context()
-    out_stage, out_bytes, DEPTH = None, 0, 2
-    free_slots: 'queue.Queue' = queue.Queue()
-    todo: 'queue.Queue' = queue.Queue()
-    failed: list = []
+    count = itertools.count()
 
-    def writer():
-        while True:
-            item = todo.get()
-            if item is None:
-                return
-            stage, k, shape, key, header, extended, index, _device_result = item      # (the tensor lives until its copy is done)
-            try:
-                stage.wait(k)                                # the D2H of this slot has landed
-                emit(index, key, stage.host_array(k, shape), header, extended)
-            except BaseException as e:                       # surfaces in the main thread
-                failed.append(e)
-            finally:
-                free_slots.put((stage, k))
+    def step(key, x, header, extended):
+        n, y = next(count), process(x)
+        print(f'# {n + 1} of {total} completed.', file=sys.stderr, end='\r')
+        return y, (n, key, header, extended)
 
-    th = threading.Thread(target=writer, daemon=True)
-    th.start()
-    retired = []
-    try:
-        for n, (key, x, header, extended) in enumerate(ImageFeed(items, ctx, headers=True)):
-            y = process(x)
-            nbytes = y.numel() * 4
-            if out_stage is None or nbytes > out_bytes:
-                # (a larger image: a new ring; the old one is closed once the writer has drained it)
-                for _ in range(DEPTH if out_stage is not None else 0):
-                    free_slots.get()
-                if out_stage is not None:
-                    retired.append(out_stage)
-                out_bytes = (nbytes + (1 << 20) - 1) & ~((1 << 20) - 1)
-                out_stage = rt.Stage(ctx, out_bytes, DEPTH)
-                for k in range(DEPTH):
-                    free_slots.put((out_stage, k))
-            stage, k = free_slots.get()
-            if failed:
-                raise failed[0]
-            stage.download(k, y)
-            todo.put((stage, k, tuple(y.shape), key, header, extended, n, y))
-            print(f'# {n + 1} of {total} completed.', file=sys.stderr, end='\r')
-    finally:
-        todo.put(None)
-        th.join()
-        for st in retired + ([out_stage] if out_stage is not None else []):
-            st.close()
-    if failed:
-        raise failed[0]
+    streaming.stream_images(items, ctx, step, emit)
     print('', file=sys.stderr)
 
 

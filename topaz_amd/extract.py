@@ -4,8 +4,9 @@ Drop-in surface of topaz/extract.py -- the names callers import keep their argum
 (NonMaximumSuppression / nms_iterator :26-104, extract_auprc / find_opt_radius :135-204, score_images :224-256,
 stream_inputs :259-263, extract_particles :266-367) -- over a different engine:
 
-  ImageFeed      a reader thread decodes micrograph i+1 straight into a pinned staging slot (tpz_stage) and queues its
-                 H2D copy while the GPU scores micrograph i; the host never waits for a copy.
+  ImageFeed      (streaming.py, imported here: `score_images` looks it up as a global of this module) a reader thread decodes
+                 micrograph i+1 straight into a pinned staging slot (tpz_stage) and queues its H2D copy while the GPU scores
+                 micrograph i; the host never waits for a copy.
   Scorer         the filled network as one HIP model (load once, one forward per image); score maps stay in HBM.
   suppression    tpz_nms_2d / _3d on the device map; only the pick table crosses PCIe.
   RadiusSearch   `--targets`: score maps cached on the device once, one device NMS + one Hungarian matching per radius.
@@ -24,23 +25,20 @@ two-tuple; the default 64/32 tiling has step 0): it is implemented here as writt
 from __future__ import annotations
 
 import os
-import queue
 import sys
-import threading
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 import torch
 
-from . import mrc
 from . import parallel
-from . import runtime as rt
 from .algorithms import match_coordinates, non_maximum_suppression, non_maximum_suppression_3d
 from .metrics import average_precision
 from .model.factory import load_model
 from .model.utils import predict_in_patches
 from .precision import check_loaded_model
+from .streaming import ImageFeed
 from .utils import files as file_utils
 from .utils.image import load_image
 from .utils.printing import report
@@ -204,162 +202,6 @@ def find_opt_radius(targets, target_scores, threshold, lo=0, hi=200, step=10, ma
 # ---------------------------------------------------------------------------------------------------------------------
 # scoring
 # ---------------------------------------------------------------------------------------------------------------------
-class ImageFeed:
-    """Iterate (path, device tensor [H, W] or [D, H, W]) with the NEXT micrograph's disk read, H2D copy and fp32 conversion
-    running under the consumer's work on the current one.  A reader thread reads into the pinned buffer of a free staging
-    slot and queues the copy; the consumer acquires the slot on its stream, uses the tensor, and the slot is released (for
-    re-use two images later) when the consumer asks for the next item.  Pixels stored as int8, int16, uint16 or float16 cross
-    to the device as stored and become fp32 there, on the copy stream; the tensor yielded is fp32 either way."""
-
-    DEPTH = 3
-
-    def __init__(self, paths: Sequence[str], ctx: 'rt.Context', headers: bool = False):
-        """headers=True: items are (path, tensor, MRC header or None, extended header or None).  An entry of `paths` that is not
-        a string is an image already in memory, (key, array, header, extended header): it takes the same ring, its key in the
-        place of the path."""
-        self.paths, self.ctx, self.headers = list(paths), ctx, headers
-        self.stage: Optional[rt.Stage] = None
-        self.slot_bytes = 0
-        self.ready: 'queue.Queue' = queue.Queue(maxsize=self.DEPTH - 1)
-        self.free: 'queue.Queue' = queue.Queue()
-        self.thread = threading.Thread(target=self._reader, daemon=True)
-        self._retired: List['rt.Stage'] = []      # outgrown rings: closed by the consumer when the feed ends
-        self._stop = threading.Event()           # the consumer left (done, or an exception): the reader must not block
-        self.uploaded_bytes = 0                  # pixel bytes queued host -> device so far (the reader thread counts them)
-
-    def _ensure_stage(self, nbytes: int) -> None:
-        # (called from the reader thread before any slot of a new, larger ring is handed out)
-        if self.stage is None or nbytes > self.slot_bytes:
-            old = self.stage
-            self.slot_bytes = (nbytes + (1 << 20) - 1) & ~((1 << 20) - 1)
-            self.stage = rt.Stage(self.ctx, self.slot_bytes, self.DEPTH)
-            while not self.free.empty():
-                self.free.get_nowait()
-            for k in range(self.DEPTH):
-                self.free.put((self.stage, k))
-            if old is not None:
-                self._retired.append(old)  # closed by the consumer when the feed ends (never from this thread: tpz_stage_free
-                                           # synchronises the ctx stream the consumer is enqueuing on)
-
-    def _get_free(self):
-        """a free slot, or None once the consumer has left"""
-        while not self._stop.is_set():
-            try:
-                return self.free.get(timeout=0.1)
-            except queue.Empty:
-                pass
-        return None
-
-    def _put_ready(self, item) -> bool:
-        while not self._stop.is_set():
-            try:
-                self.ready.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                pass
-        return False
-
-    def _reader(self) -> None:
-        try:
-            torch.cuda.set_device(self.ctx.device)
-            class _Left(Exception):
-                pass
-
-            held = []
-
-            def pinned(shape, dtype=np.float32):
-                """the pinned buffer of a free staging slot for an image of that shape (the ring grows when it must).  A dtype
-                the device decodes (mrc.STORED_MODES): the slot holds the fp32 image and, behind it, the stored pixels"""
-                n = int(np.prod(shape))
-                mode = mrc.STORED_MODES.get(np.dtype(dtype))
-                nbytes = n * 4 if mode is None else rt.Stage.decode_bytes(self.ctx, mode, n)
-                if self.stage is None or nbytes > self.slot_bytes:
-                    # wait until every slot of the old ring came back, then grow
-                    if self.stage is not None:
-                        for _ in range(self.DEPTH):
-                            if self._get_free() is None:
-                                raise _Left()
-                    self._ensure_stage(nbytes)
-                slot = self._get_free()
-                if slot is None:
-                    raise _Left()
-                # the slot's previous upload may still be queued (a consumer that only enqueues runs ahead of the copy
-                # stream): the pinned buffer is refilled only after that copy has read it
-                slot[0].wait(slot[1])
-                held[:] = [slot, n, mode]
-                return slot[0].host_array(slot[1], shape, np.float32 if mode is None else dtype)
-
-            for path in self.paths:
-                header = extended = None
-                try:
-                    # an MRC file is read straight into pinned memory IN THE TYPE IT STORES (float32, or int8 / int16 / uint16 /
-                    # float16, which the device decodes: Stage.upload_decode); anything else is loaded and converted into it; so
-                    # is an image the caller already holds (a section of a stack), which keeps a stored type of those four too
-                    in_memory = not isinstance(path, str)
-                    if in_memory:
-                        path, image, header, extended = path
-                    got = mrc.read_stored_into(path, pinned) if not in_memory and os.path.splitext(path)[1] == '.mrc' else None
-                    if got is not None:
-                        host, header, extended = got
-                    else:
-                        if not in_memory:
-                            loaded = load_image(path, make_image=False)
-                            image, header, extended = loaded if isinstance(loaded, tuple) else (loaded, None, None)
-                        image = np.asarray(image)
-                        host = pinned(image.shape, image.dtype if image.dtype in mrc.STORED_MODES else np.float32)
-                        np.copyto(host, image, casting='unsafe')
-                except _Left:
-                    return
-                (stage, k), n, mode = held
-                if mode is None:
-                    stage.upload(k, 4 * n)
-                else:
-                    stage.upload_decode(k, mode, n)
-                self.uploaded_bytes += n * host.dtype.itemsize
-                if not self._put_ready((path, stage, k, host.shape, header, extended)):
-                    return
-            self._put_ready(None)
-        except BaseException as e:                                            # surface reader failures in the consumer
-            self._put_ready(e)
-
-    def __iter__(self) -> Iterator[Tuple[str, torch.Tensor]]:
-        self.thread.start()
-        held = None
-        try:
-            while True:
-                if held is not None:            # the consumer came back for more: it is done with the previous tensor
-                    held[0].release(held[1])
-                    self.free.put(held)
-                    held = None
-                item = self.ready.get()
-                if item is None:
-                    return
-                if isinstance(item, BaseException):
-                    raise item
-                path, stage, k, shape, header, extended = item
-                stage.acquire(k)
-                held = (stage, k)
-                if self.headers:
-                    yield path, stage.device_tensor(k, shape), header, extended
-                else:
-                    yield path, stage.device_tensor(k, shape)
-        finally:
-            if held is not None:
-                held[0].release(held[1])
-            # the consumer is leaving (exhausted, early exit or exception): unblock and join the reader, then close the rings
-            # from THIS thread (the one that enqueues on the ctx stream)
-            self._stop.set()
-            if self.thread.is_alive():
-                self.thread.join(timeout=30)
-            if not self.thread.is_alive():
-                for st in self._retired:
-                    st.close()
-                self._retired = []
-                if self.stage is not None:
-                    self.stage.close()
-                    self.stage = None
-
-
 class Scorer:
     """the filled scoring network on one MI355X"""
 

@@ -8,7 +8,8 @@ them (`np.quantile`, `np.random.choice` on the global NumPy RNG), so a seeded ru
 
 That is the per-file path (`Normalize`, `normalize`, `norm_fit`).  `normalize_images`, behind the two commands, streams the files
 through the device instead (second half of this file): the same results byte for byte, with the sub-sample
-gathered, the quantiles selected, all initialisations fitted per pass and the image normalised without leaving the GPU."""
+gathered, the quantiles selected, all initialisations fitted per pass and the image normalised without leaving the GPU; the feed
+that brings the files in, the pinned ring that carries the results out and the loop between them are streaming.py's."""
 from __future__ import annotations
 
 import json
@@ -17,6 +18,8 @@ import sys
 from typing import List
 
 import numpy as np
+
+from . import streaming
 
 INIT_PIS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.98, 1.0)     # stats.py:91
 _FIT_ARRAYS = ('mus', 'stds', 'pis', 'logps')                                    # per-initialisation results (metadata)
@@ -132,9 +135,9 @@ class Normalize:
 
 
 # ---- the device-resident stream behind `topaz normalize` / `topaz preprocess` -------------------------------------------------
-# Every pass over the pixels of `Normalize` above, on the device, image after image: ImageFeed decodes the next file into pinned
-# memory while this one is down-sampled, sub-sampled (gather), split at its quantiles (radix select), fitted (all initialisations
-# per pass) and normalised; the result leaves through a pinned ring that a writer thread drains.  `Normalize`, `normalize` and
+# Every pass over the pixels of `Normalize` above, on the device, image after image (streaming.stream_images): the feed decodes the
+# next file into pinned memory while this one is down-sampled, sub-sampled (gather), split at its quantiles (radix select), fitted
+# (all initialisations per pass) and normalised; the result leaves through the pinned result ring that a writer thread drains.  `Normalize`, `normalize` and
 # `norm_fit` stay as the per-file path the stream is tested against: same files, byte for byte.
 
 def _quantile_brackets(n: int, q):
@@ -232,88 +235,41 @@ class DevicePreprocess:
 
 def _normalize_stream(paths: List[str], dest: str, scale: int, fit_args: dict, metadata: bool, formats: List[str],
                       verbose: bool) -> None:
-    """the loop of `normalize_images` over this process's files (structure: denoise._denoise_stream_device)"""
-    import queue
-    import threading
+    """the loop of `normalize_images` over this process's files: streaming.stream_images around the two halves below"""
     from . import runtime as rt
-    from .extract import ImageFeed
     from .utils.image import downsample_device, save_image
     if not paths:
         return
     affine = fit_args['method'] == 'affine'
-    ctx = rt.get_context()
-    out_stage, out_bytes, DEPTH = None, 0, 2
-    free_slots: 'queue.Queue' = queue.Queue()
-    todo: 'queue.Queue' = queue.Queue()
-    failed: list = []
 
-    def writer():
-        while True:
-            item = todo.get()
-            if item is None:
-                return
-            stage, k, shape, path, header, extended, meta, _device_result = item       # (the tensor lives until its copy is done)
-            try:
-                if not failed:
-                    stage.wait(k)                            # the D2H of this slot has landed
-                    pixels = stage.host_array(k, shape)
-                    if affine:
-                        # --affine keeps numpy's own statistics: the (down-sampled) image came down, the per-file expressions
-                        # run here, under the GPU's work on the next image
-                        pixels, meta = normalize(pixels, **fit_args)
-                    name = os.path.splitext(os.path.basename(path))[0]
-                    stem = os.path.join(dest, name)
-                    for fmt in formats:
-                        save_image(pixels, stem, f=fmt, header=header, extended_header=extended)
-                    if metadata:
-                        with open(stem + '.metadata.json', 'w') as fh:
-                            json.dump(_jsonable(meta), fh, indent=4)
-                    if verbose:
-                        print('# processed:', name, file=sys.stderr)
-            except BaseException as e:                       # surfaces in the main thread
-                failed.append(e)
-            finally:
-                free_slots.put((stage, k))
+    def process(path, x, header, extended):
+        if scale > 1:
+            x = downsample_device(x, scale)
+            if header:
+                header = header._replace(ny=x.shape[0], nx=x.shape[1])
+        if affine:
+            # (a copy when x is still the feed's own slot, which the feed re-uses once the next image is asked for)
+            y, meta = (x if scale > 1 else x.clone()), None
+        else:
+            y, meta = normalize_device(x, **fit_args)        # every RNG draw happens here, in path order
+        return y, (path, header, extended, meta)
 
-    th = threading.Thread(target=writer, daemon=True)
-    th.start()
-    retired = []
-    feed = iter(ImageFeed(paths, ctx, headers=True))
-    try:
-        for path, x, header, extended in feed:
-            if scale > 1:
-                x = downsample_device(x, scale)
-                if header:
-                    header = header._replace(ny=x.shape[0], nx=x.shape[1])
-            if affine:
-                # (a copy when x is still the feed's own slot, which the feed re-uses once the next image is asked for)
-                y, meta = (x if scale > 1 else x.clone()), None
-            else:
-                y, meta = normalize_device(x, **fit_args)    # every RNG draw happens here, in path order
-            nbytes = y.numel() * 4
-            if out_stage is None or nbytes > out_bytes:
-                # (a larger image: a new ring; the old one is closed once the writer has drained it)
-                for _ in range(DEPTH if out_stage is not None else 0):
-                    free_slots.get()
-                if out_stage is not None:
-                    retired.append(out_stage)
-                out_bytes = (nbytes + (1 << 20) - 1) & ~((1 << 20) - 1)
-                out_stage = rt.Stage(ctx, out_bytes, DEPTH)
-                for k in range(DEPTH):
-                    free_slots.put((out_stage, k))
-            stage, k = free_slots.get()
-            if failed:
-                raise failed[0]
-            stage.download(k, y)
-            todo.put((stage, k, tuple(y.shape), path, header, extended, meta, y))
-    finally:
-        feed.close()                                         # joins the reader thread
-        todo.put(None)
-        th.join()
-        for st in retired + ([out_stage] if out_stage is not None else []):
-            st.close()
-    if failed:
-        raise failed[0]
+    def write(pixels, path, header, extended, meta):
+        if affine:
+            # --affine keeps numpy's own statistics: the (down-sampled) image came down, the per-file expressions run here,
+            # under the GPU's work on the next image
+            pixels, meta = normalize(pixels, **fit_args)
+        name = os.path.splitext(os.path.basename(path))[0]
+        stem = os.path.join(dest, name)
+        for fmt in formats:
+            save_image(pixels, stem, f=fmt, header=header, extended_header=extended)
+        if metadata:
+            with open(stem + '.metadata.json', 'w') as fh:
+                json.dump(_jsonable(meta), fh, indent=4)
+        if verbose:
+            print('# processed:', name, file=sys.stderr)
+
+    streaming.stream_images(paths, rt.get_context(), process, write)
 
 
 def normalize_images(paths: List[str], dest: str, num_workers: int, scale: int, affine: bool, niters: int, alpha: float,

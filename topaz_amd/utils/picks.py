@@ -4,9 +4,9 @@ stack with a RELION STAR file next to it.
 The work is split in two.  plan_particle_stack reads the pick table, the micrograph headers and the optional metadata STAR on
 the host and fixes everything that does not depend on pixel values -- the particle order, the stack header and the STAR text --
 and refuses bad input before a byte is written.  write_particle_stack then streams the micrographs through the MI355X
-(extract.ImageFeed: micrograph i+1 is decoded and uploaded while micrograph i is cropped), cuts the boxes in chunks that fit a
+(streaming.ImageFeed: micrograph i+1 is decoded and uploaded while micrograph i is cropped), cuts the boxes in chunks that fit a
 device byte budget (tpz_particle_stack: one launch per chunk, four with --resize) and hands each chunk through a pinned staging
-slot to a writer thread, so the stack is written once and never held whole on the host.
+slot to a writer thread (streaming.ResultRing), so the stack is written once and never held whole on the host.
 
 Both halves are shared with `topaz extract --particle-stack` (ExtractStack), which cuts the boxes of a micrograph while it is
 resident for picking: plan_from_records builds the header and the STAR text from picks held in memory, StackWriter is the
@@ -34,6 +34,7 @@ import numpy as np
 import pandas as pd
 
 from .. import mrc
+from .. import streaming
 from .files import read_star, write_star
 
 DEFAULT_BUDGET = 256 << 20      # device bytes of one chunk of particles (output plus the resize intermediates)
@@ -188,9 +189,9 @@ def particle_offset(base: int, counts: Sequence[int], rank: int) -> Tuple[int, i
 class StackWriter:
     """The streaming half of a particle stack, shared by `particle_stack` and `extract --particle-stack`.  cut() crops,
     standardises (and resizes) the picks of one resident micrograph in chunks of the device byte budget and hands every chunk
-    through a slot of a pinned rt.Stage ring to a writer thread.  The thread puts the chunk at the byte the global index of its
-    first particle fixes (os.pwrite): the ranks of a sharded job write one file, and a stack whose length is only known after the
-    last micrograph gets its header last (seal_particle_stack).  Every rank opens the same file and none truncates it."""
+    to a streaming.ResultRing, whose writer thread puts the chunk at the byte the global index of its first particle fixes
+    (os.pwrite): the ranks of a sharded job write one file, and a stack whose length is only known after the last micrograph
+    gets its header last (seal_particle_stack).  Every rank opens the same file and none truncates it."""
 
     DEPTH = 2
 
@@ -198,87 +199,37 @@ class StackWriter:
                  placeholder: bool = True):
         """capacity: particles per ring slot to start with (it grows to the largest chunk seen); placeholder: write the 1024
         bytes the header will replace (rank 0)"""
-        import queue
-        import threading
         self.ctx, self.path, self.S, self.R, self.mz = ctx, path, size, resize, mz
         self.ops = resize_operators(size, resize) if resize != size else None
         self.out_bytes = 4 * mz * resize * resize
         dev_bytes = self.out_bytes + (4 * mz * (size * size + 2 * size * resize) if resize != size else 0)
         self.per_chunk = max(1, int(budget_bytes) // dev_bytes)
-        self.stage = None
-        self.capacity = 0
-        self.free_slots: 'queue.Queue' = queue.Queue()
-        self.todo: 'queue.Queue' = queue.Queue()
-        self.failed: list = []
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT, 0o666)
         if placeholder:
             os.pwrite(self.fd, bytes(1024), 0)
+        self.ring = streaming.ResultRing(ctx, lambda chunk, at: streaming.pwrite_all(self.fd, chunk, at), self.DEPTH)
         if capacity:
-            self._ensure(min(self.per_chunk, capacity))
-        self.thread = threading.Thread(target=self._writer, daemon=True)
-        self.thread.start()
-
-    def _ensure(self, n: int) -> None:
-        """a ring whose slots hold n particles"""
-        from .. import runtime as rt
-        if n <= self.capacity:
-            return
-        if self.stage is not None:
-            for _ in range(self.DEPTH):                         # every chunk in flight has been written
-                self.free_slots.get()
-            self.stage.close()
-            self.stage = None
-            self.check()
-        self.capacity = n
-        self.stage = rt.Stage(self.ctx, n * self.out_bytes, self.DEPTH)
-        for k in range(self.DEPTH):
-            self.free_slots.put(k)
-
-    def _writer(self) -> None:
-        while True:
-            item = self.todo.get()
-            if item is None:
-                return
-            k, n_floats, at, _device_chunk = item               # (the tensor lives until its copy has landed)
-            try:
-                if not self.failed:
-                    self.stage.wait(k)
-                    view = memoryview(self.stage.host_array(k, (n_floats,))).cast('B')
-                    done = 0
-                    while done < len(view):
-                        done += os.pwrite(self.fd, view[done:], at + done)
-            except BaseException as e:                          # surfaces in the main thread
-                self.failed.append(e)
-            finally:
-                self.free_slots.put(k)
+            self.ring.reserve(min(self.per_chunk, capacity) * self.out_bytes)
 
     def check(self) -> None:
-        if self.failed:
-            raise self.failed[0]
+        self.ring.check()
 
     def cut(self, img, xy: np.ndarray, first: int) -> None:
         """the particles at xy ([n, 2] int32) of the resident micrograph img are particles first .. first + n - 1 of the stack"""
         from .. import runtime as rt
         for c0 in range(0, len(xy), self.per_chunk):
             part = xy[c0:c0 + self.per_chunk]
-            self._ensure(len(part))
+            self.ring.reserve(len(part) * self.out_bytes)       # (a growth drains the ring: before the launch, not after it)
             out = rt.particle_stack(img, part, self.S, self.R, self.ops, ctx=self.ctx)
-            k = self.free_slots.get()
-            self.check()
-            self.stage.download(k, out)
-            self.todo.put((k, out.numel(), 1024 + self.out_bytes * (first + c0), out))
+            self.ring.put(out, 1024 + self.out_bytes * (first + c0))
 
     def close(self) -> None:
-        """wait for the last write, free the ring, close the file (idempotent; a writer failure stays in `failed`)"""
-        if self.thread is None:
+        """wait for the last write, free the ring, close the file (idempotent; a writer failure stays available to check())"""
+        if self.fd is None:
             return
-        self.todo.put(None)
-        self.thread.join()
-        self.thread = None
-        if self.stage is not None:
-            self.stage.close()
-            self.stage = None
+        self.ring.close()
         os.close(self.fd)
+        self.fd = None
 
 
 def seal_particle_stack(path: str, header: bytes, n: int, out_bytes: int, star_path: str, star: str) -> None:
@@ -302,7 +253,6 @@ def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAUL
 
     from .. import parallel
     from .. import runtime as rt
-    from ..extract import ImageFeed
     log = sys.stderr if log is None else log
     rank, local_rank, world = ranks
     torch.cuda.set_device(device)
@@ -313,7 +263,7 @@ def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAUL
     writer = StackWriter(ctx, plan.output, plan.size, plan.resize, plan.mz, budget_bytes,
                          capacity=max([len(m.xy) for m in mics] or [0]), placeholder=(rank == 0))
     try:
-        for j, (path, img) in enumerate(ImageFeed([m.path for m in mics], ctx)):
+        for j, (path, img) in enumerate(streaming.ImageFeed([m.path for m in mics], ctx)):
             m = mics[j]
             if tuple(img.shape) != tuple(m.shape):
                 raise ValueError(f'particle_stack: {path} holds {tuple(img.shape)} pixels, its header says {m.shape}')
