@@ -180,6 +180,24 @@ int tpz_normalize_cutoff(tpz_ctx* ctx, const float* d_x, size_t n, float mean, f
  * 16-byte aligned (one 16-byte load per lane), d_out 4-byte (16-byte for the vector stores; otherwise a slower scalar loop).
  * n == 0 does nothing.  The buffers must not overlap.  Asynchronous; one launch. */
 int tpz_decode(tpz_ctx* ctx, const void* d_raw, int mrc_mode, size_t n, float* d_out);
+/* The other direction: n fp32 pixels at d_in become the pixels a file stores, at d_out, on the ctx stream.
+ *   TPZ_ENC_F16  binary16 (MRC mode 12), 2 bytes per pixel: the bits of numpy's astype(np.float16) for EVERY fp32 input -- round
+ *                to nearest, ties to even; half subnormals are produced, not flushed; |x| >= 65520 becomes +-inf; infinities and
+ *                signed zeros are kept; a NaN becomes sign | (0x7c00 + (mantissa >> 13)), plus 1 where that would read as an
+ *                infinity (npy_floatbits_to_halfbits).  Integer arithmetic on the bits, so no float mode of the device enters.
+ *                params is ignored (may be NULL).  d_overflow: NULL, or a device unsigned long long to which the number of FINITE
+ *                inputs stored as +-inf is ADDED (the caller zeroes it).
+ *   TPZ_ENC_U8   one byte per pixel, params = {mi, ma} on the host: the bytes of numpy's
+ *                round(clip(255 * (x - mi) / (ma - mi), 0, 255)).astype(uint8) on a float32 array -- every fp32 operation rounded
+ *                on its own, in that order, IEEE division, ties to even; ma - mi is formed in fp32 from the fp32 params, so
+ *                these are numpy's bytes when mi, ma and ma - mi are exact in fp32 (-3, 3: the pair of save_image).  NaN is
+ *                stored as 0.  d_overflow is ignored.
+ * Any other enc is an error.  d_in must be 4-byte aligned and d_out aligned to its pixel; when both are 16-byte aligned a lane
+ * takes 16-byte loads and writes one 16-byte store (8 / 16 pixels), otherwise every pixel goes through a scalar loop.  Nothing
+ * at d_out beyond n pixels is written.  n == 0 does nothing.  The buffers must not overlap.  Asynchronous; one launch. */
+enum { TPZ_ENC_F16 = 12, TPZ_ENC_U8 = 8 };
+int tpz_encode(tpz_ctx* ctx, const float* d_in, size_t n, int enc, const float* params, void* d_out,
+               unsigned long long* d_overflow);
 /* 1->1 channel 2-D filter with zero "same" padding: GaussianDenoise / InvGaussianFilter /
  * AffineFilter.forward (topaz/filters.py:28-96).  h_w is the [k][k] kernel on the host. */
 int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_w, int k, float bias,
@@ -262,6 +280,16 @@ int tpz_stage_wait(tpz_stage* st, int slot);
  * tpz_prof_launches (it is not on the ctx stream). */
 size_t tpz_stage_decode_bytes(int mrc_mode, size_t n);
 int tpz_stage_h2d_decode(tpz_stage* st, int slot, int mrc_mode, size_t n);
+/* The mirror image on the way out: tpz_stage_d2h for a result that is stored as float16 or as bytes (enc, params: tpz_encode).
+ * `produced` is recorded on the ctx stream; the copy stream waits for it, clears the slot's 8-byte overflow counter, encodes the
+ * n fp32 pixels at d_src into the slot's DEVICE buffer -- encoded pixels at its start, the counter (unsigned long long) at the
+ * next multiple of 256 bytes -- and brings pixels and counter into the pinned buffer with one copy, at the same offsets; then
+ * the slot's copy event is recorded.  After tpz_stage_wait the pinned slot holds the encoded pixels and the counter: half or a
+ * quarter of the bytes crossed the bus and the host converted nothing.  The slot must hold tpz_stage_encode_bytes(enc, n) bytes
+ * (the pixels rounded up to 256, plus 256; 0 for an unknown enc).  An unknown enc, a slot that is too small or a NULL pointer
+ * is an error and queues nothing.  The launch is not counted by tpz_prof_launches (it is not on the ctx stream). */
+size_t tpz_stage_encode_bytes(int enc, size_t n);
+int tpz_stage_d2h_encode(tpz_stage* st, int slot, const float* d_src, size_t n, int enc, const float* params);
 /* Host-pointer forms of the three calls of the path (synchronous; plain pageable or pinned memory), the signatures
  * SURVEY.md 8(b) sketches: model(x) on a numpy image (extract.py:247-249), Denoise.denoise (denoise.py:327-332),
  * non_maximum_suppression (algorithms.py:25-63).  Each stages through an internal ring owned by the ctx. */

@@ -17,6 +17,8 @@ TPZ_OP_CONV = 1
 TPZ_OP_MAXPOOL2 = 2
 TPZ_OP_MAXPOOL = 3
 TPZ_OP_AVGPOOL = 4
+TPZ_ENC_F16 = 12
+TPZ_ENC_U8 = 8
 
 
 class TpzLayer(C.Structure):
@@ -92,6 +94,9 @@ _SIGNATURES = {
     'tpz_decode': (C.c_int, [_P, _P, C.c_int, C.c_size_t, _P]),
     'tpz_stage_decode_bytes': (C.c_size_t, [C.c_int, C.c_size_t]),
     'tpz_stage_h2d_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t]),
+    'tpz_encode': (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float), _P, _P]),
+    'tpz_stage_encode_bytes': (C.c_size_t, [C.c_int, C.c_size_t]),
+    'tpz_stage_d2h_encode': (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     'tpz_score_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     'tpz_denoise_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'tpz_nms_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int, C.POINTER(C.c_int)]),

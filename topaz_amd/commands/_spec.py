@@ -19,6 +19,10 @@ _PRECISION: Flag = (('--precision-check',), dict(choices=['auto', 'always', 'nev
                                                 help='measure the 2xf16 path of each loaded model against its fp32 result on one seeded '
                                                      'tile and run a model above 1e-4 on the fp32 kernels: auto checks model files '
                                                      '(user-trained), always the pretrained aliases too, never nothing'))
+_FLOAT16: Flag = (('--float16',), dict(action='store_true',
+                                      help='store the MRC output as float16 (MRC mode 12, what RELION writes with --float16): half '
+                                           'the bytes, encoded on the GPU with the rounding of numpy\'s astype(float16); values '
+                                           'beyond +-65504 become inf and are reported on stderr.  MRC output only'))
 _THREADS: Flag = (('-j', '--num-threads'), dict(type=int, default=0, help='host threads for torch (0: library default, <0: all cores)'))
 
 EXTRACT: List[Flag] = [
@@ -75,6 +79,7 @@ EXTRACT: List[Flag] = [
                                           '--threshold`; default: -inf).  The pick table is not filtered by it')),
     (('--particle-metadata',), dict(metavar='STAR', help='--particle-stack: per-micrograph metadata merged into the output STAR '
                                                          '(`particle_stack --metadata`)')),
+    (('--float16',), dict(action='store_true', help='--particle-stack: store the stack as float16 (MRC mode 12)')),
 ]
 
 _TRAINING_ONLY = 'training option (not supported on this path)'
@@ -117,6 +122,7 @@ DENOISE: List[Flag] = [
     _THREADS,
     _GPUS,
     _PRECISION,
+    _FLOAT16,
 ]
 
 DENOISE3D: List[Flag] = [
@@ -147,6 +153,7 @@ DENOISE3D: List[Flag] = [
     (('-d', '--device'), dict(type=int, default=-2, help='-2: every visible MI355X (one rank process each; LOCAL_RANK when already under a launcher); >=0: that GPU; -1 is an error')),
     _GPUS,
     _PRECISION,
+    _FLOAT16,
 ]
 
 SEGMENT: List[Flag] = [
@@ -166,6 +173,7 @@ DOWNSAMPLE: List[Flag] = [
     (('-s', '--scale'), dict(type=int, default=4, help='integer reduction factor')),
     (('-o', '--output'), dict(help='file to write')),
     (('-v', '--verbose'), dict(action='store_true', help='report the shapes')),
+    _FLOAT16,
 ]
 
 
@@ -187,6 +195,7 @@ NORMALIZE: List[Flag] = [
     (('--format',), dict(dest='format_', default='mrc', help='comma separated list of mrc, tiff, png')),
     (('-v', '--verbose'), dict(action='store_true', help='name every processed file')),
     _GPUS,
+    _FLOAT16,
 ]
 
 
@@ -201,8 +210,8 @@ PARTICLE_STACK: List[Flag] = [
     (('--metadata',), dict(help='STAR file of per-micrograph metadata merged into the output STAR on MicrographName')),
 ]
 # kept apart from the table above, which mirrors the reference's parser flag for flag (tests/test_cpu_particle_stack.py): the
-# ranks cut the plan's micrographs i = rank (mod N) into the one output file
-PARTICLE_STACK_RANKS: List[Flag] = [_GPUS]
+# ranks cut the plan's micrographs i = rank (mod N) into the one output file; --float16 stores the stack as MRC mode 12
+PARTICLE_STACK_RANKS: List[Flag] = [_GPUS, _FLOAT16]
 
 
 def build_parser(flags: List[Flag], description: str, parser: argparse.ArgumentParser = None) -> argparse.ArgumentParser:

@@ -5,7 +5,7 @@ import sys
 
 from .. import denoise as dn
 from ..cuda import set_device
-from ..denoise import Denoise, denoise_stack, denoise_stream
+from ..denoise import Denoise, denoise_stack, denoise_stack_stored, denoise_stream
 from ..precision import check_loaded_model
 
 name = 'denoise'
@@ -20,6 +20,9 @@ def add_arguments(parser=None):
 def main(args):
     from ..torch import set_num_threads
     from .. import parallel
+    from ..mrc import check_float16_formats
+    float16 = getattr(args, 'float16', False)
+    check_float16_formats(float16, ['mrc'] if args.stack else [args.format_])      # (before a model or an image is read)
     set_num_threads(args.num_threads)
     _, local_rank, world = parallel.init_from_env()
     device = parallel.rank_device(local_rank) if world > 1 else args.device
@@ -40,11 +43,15 @@ def main(args):
     if len(args.micrographs) < 1:
         return
     if args.stack:
+        if float16:
+            return denoise_stack_stored(args.micrographs[0], args.output, models, args.lowpass, args.pixel_cutoff, gaus,
+                                        inv_gaus, args.deconvolve, args.deconv_patch, args.patch_size, args.patch_padding,
+                                        normalize, use_cuda, float16=True)
         return denoise_stack(args.micrographs[0], args.output, models, args.lowpass, args.pixel_cutoff, gaus, inv_gaus,
                              args.deconvolve, args.deconv_patch, args.patch_size, args.patch_padding, normalize, use_cuda)
     return denoise_stream(args.micrographs, args.output, args.format_, args.suffix, models, args.lowpass,
                           args.pixel_cutoff, gaus, inv_gaus, args.deconvolve, args.deconv_patch, args.patch_size,
-                          args.patch_padding, normalize, use_cuda, return_images=False)
+                          args.patch_padding, normalize, use_cuda, return_images=False, float16=float16)
 
 
 if __name__ == '__main__':

@@ -43,7 +43,7 @@ def main(args):
           file=sys.stderr)
     return denoise_tomogram_stream(volumes=args.volumes, model=denoiser, output_path=args.output, suffix=args.suffix,
                                    gaus=args.gaussian, patch_size=args.patch_size, padding=args.patch_padding,
-                                   verbose=True, use_cuda=True)
+                                   verbose=True, use_cuda=True, float16=getattr(args, 'float16', False))
 
 
 if __name__ == '__main__':

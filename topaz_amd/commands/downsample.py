@@ -12,7 +12,7 @@ def add_arguments(parser=None):
 
 def main(args):
     from ..utils.image import downsample_file
-    downsample_file(args.file, args.scale, args.output, args.verbose)
+    downsample_file(args.file, args.scale, args.output, args.verbose, float16=getattr(args, 'float16', False))
 
 
 if __name__ == '__main__':

@@ -23,7 +23,10 @@ def main(args):
     stack = dict(particle_stack=getattr(args, 'particle_stack', None), particle_size=getattr(args, 'particle_size', None),
                  particle_resize=getattr(args, 'particle_resize', -1),
                  particle_threshold=getattr(args, 'particle_threshold', -float('inf')),
-                 particle_metadata=getattr(args, 'particle_metadata', None))
+                 particle_metadata=getattr(args, 'particle_metadata', None),
+                 particle_float16=getattr(args, 'float16', False))
+    if stack['particle_float16'] and not stack['particle_stack']:
+        raise ValueError('--float16 is the stored type of the --particle-stack file: it needs --particle-stack')
     check_particle_stack_args(stack['particle_stack'], stack['particle_size'], stack['particle_resize'], args.model, args.dims,
                               args.targets, args.only_validate)
     preprocess = None

@@ -15,10 +15,13 @@ def main(args):
     from .. import parallel
     from ..cuda import set_device
     from ..stats import normalize_images
+    from ..mrc import check_float16_formats
+    float16 = getattr(args, 'float16', False)
+    check_float16_formats(float16, args.format_.split(','))         # (before a device is touched or a file read)
     _, local_rank, world = parallel.init_from_env()
     set_device(parallel.rank_device(local_rank) if world > 1 else args.device)
     normalize_images(args.files, args.destdir, 0, args.scale, args.affine, args.niters, args.alpha, args.beta,
-                     args.sample, args.metadata, args.format_.split(','), True, args.verbose)
+                     args.sample, args.metadata, args.format_.split(','), True, args.verbose, float16=float16)
 
 
 if __name__ == '__main__':

@@ -44,6 +44,41 @@ __host__ __device__ static inline unsigned f16_bits_to_f32_bits(unsigned h) {
 // out[i] = (float)raw[i] for n pixels of MRC mode 0 / 1 / 6 / 12 (any other mode: hipErrorInvalidValue).  raw must be 16-byte
 // aligned; out 4-byte (16-byte for the vector body, otherwise every pixel takes the scalar loop).  One launch; n == 0: none.
 hipError_t launch_decode(const void* raw, int mrc_mode, size_t n, float* out, hipStream_t s);
+
+// fp32 -> stored pixels (encode_kernel).  The encodings of tpz_encode (topaz_hip.h: TPZ_ENC_F16, TPZ_ENC_U8) and their bytes per
+// pixel; 0 for anything else.
+enum { ENC_F16 = 12, ENC_U8 = 8 };
+static inline size_t encoded_itemsize(int enc) { return enc == ENC_F16 ? 2 : enc == ENC_U8 ? 1 : 0; }
+// The binary16 bits of an fp32 value, by integer operations only: what numpy's astype(np.float16) gives for every one of the 2^32
+// patterns (npy_floatbits_to_halfbits) -- round to nearest, ties to even, at the 13 dropped mantissa bits of a half normal and at
+// the 14..24 dropped bits of a half subnormal (a carry walks into the exponent, up to the smallest normal and up to infinity, by
+// itself); |x| >= 65520 (the midpoint of 65504 and 2^16) is +-inf; below 2^-25, fp32 subnormals included, +-0; a NaN keeps its sign
+// and the top 10 payload bits, with bit 0 set when those are all zero.
+__host__ __device__ static inline unsigned f32_bits_to_f16_bits(unsigned f) {
+    const unsigned sign = (f >> 16) & 0x8000u, a = f & 0x7fffffffu;
+    if (a >= 0x7f800000u) {                                                    // inf / NaN
+        if (a == 0x7f800000u) return sign | 0x7c00u;
+        const unsigned m = 0x7c00u + ((a & 0x007fffffu) >> 13);
+        return sign | (m == 0x7c00u ? 0x7c01u : m);
+    }
+    if (a >= 0x477ff000u) return sign | 0x7c00u;                               // >= 65520: rounds to infinity
+    const unsigned e = a >> 23;
+    if (e >= 113u) {                                                           // half normal: exponent rebias 127 -> 15
+        const unsigned h = (a - (112u << 23)) >> 13, rem = a & 0x1fffu;
+        return sign | (h + ((rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ? 1u : 0u));
+    }
+    if (e < 102u) return sign;                                                 // below 2^-25: zero
+    // half subnormal: the 24-bit significand in units of 2^(e - 150), stored in units of 2^-24
+    const unsigned m = (a & 0x007fffffu) | 0x00800000u, shift = 126u - e;      // 14 .. 24
+    const unsigned h = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    return sign | (h + ((rem > half || (rem == half && (h & 1u))) ? 1u : 0u));
+}
+// out[i] = encoded in[i] for n pixels; enc ENC_F16 (2 bytes per pixel) or ENC_U8 (1 byte, with mi and ma of quantize); any other
+// enc: hipErrorInvalidValue.  in must be 4-byte aligned, out aligned to its pixel; both 16-byte aligned for the vector body,
+// otherwise every pixel takes the scalar loop.  overflow (ENC_F16; may be null): += finite inputs stored as +-inf.  One launch;
+// n == 0: none.
+hipError_t launch_encode(const float* in, int enc, size_t n, float mi, float ma, void* out, unsigned long long* overflow,
+                         hipStream_t s);
 hipError_t launch_transpose(const float* in, float* out, int R, int Cc, hipStream_t s);
 hipError_t launch_maxpool2_split(const void* in, void* out, int C, int D, int H, int W, int dims, hipStream_t s);
 hipError_t launch_maxpoolz_split(const float* in, float* out, int C, int D, int H, int W, hipStream_t s);   // z pairs only (split cells)

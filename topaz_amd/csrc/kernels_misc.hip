@@ -509,6 +509,80 @@ hipError_t launch_decode(const void* raw, int mrc_mode, size_t n, float* out, hi
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// fp32 -> stored pixels, the mirror image: float16 (MRC mode 12; f32_bits_to_f16_bits, the bits of numpy's astype(float16)) or the
+// uint8 of utils.image.quantize, round(clip(255 * (x - mi) / (ma - mi), 0, 255)) with every fp32 operation rounded on its own as
+// numpy rounds it (the *_rn intrinsics keep the compiler from contracting or reassociating them; den = ma - mi is formed once, in
+// fp32, by the launcher).  fmaxf / fminf drop a NaN operand, so NaN is stored as 0.  Each lane takes two (four) 16-byte loads
+// and writes one 16-byte store of 8 (16) pixels; the n % 8 (n % 16) pixels behind go one by one; both loops stride over the
+// grid.  No LDS: a workgroup is one wave, which sums its count of finite inputs stored as +-inf over its lanes and adds it to
+// *overflow with one atomicAdd, and only when there is something to add.  The pass is bound by the 4n bytes it reads.
+// ------------------------------------------------------------------------------------------
+template <int ENC>
+__device__ __forceinline__ unsigned f32_to_stored(float x, float mi, float den, unsigned& ovf) {
+    if (ENC == ENC_F16) {
+        const unsigned f = __float_as_uint(x), h = f32_bits_to_f16_bits(f);
+        ovf += ((h & 0x7fffu) == 0x7c00u && (f & 0x7fffffffu) < 0x7f800000u) ? 1u : 0u;
+        return h;
+    }
+    const float t = __fdiv_rn(__fmul_rn(255.0f, __fsub_rn(x, mi)), den);
+    return (unsigned)(int)rintf(fminf(fmaxf(t, 0.0f), 255.0f));
+}
+
+template <int ENC>
+__global__ __launch_bounds__(64) void encode_kernel(const float* __restrict__ in, void* __restrict__ out, size_t n_vec, size_t n,
+                                                    float mi, float den, unsigned long long* __restrict__ overflow) {
+    constexpr int EPL = ENC == ENC_F16 ? 8 : 16;                      // pixels per 16-byte store
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x, stride = (size_t)gridDim.x * 64;
+    unsigned ovf = 0;
+    for (size_t c = t; c < n_vec; c += stride) {
+        const float4* p = (const float4*)(in + c * EPL);
+        unsigned w[4];
+        if (ENC == ENC_F16) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float4 v = p[k];
+                w[2 * k] = f32_to_stored<ENC>(v.x, mi, den, ovf) | (f32_to_stored<ENC>(v.y, mi, den, ovf) << 16);
+                w[2 * k + 1] = f32_to_stored<ENC>(v.z, mi, den, ovf) | (f32_to_stored<ENC>(v.w, mi, den, ovf) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 v = p[k];
+                w[k] = f32_to_stored<ENC>(v.x, mi, den, ovf) | (f32_to_stored<ENC>(v.y, mi, den, ovf) << 8) |
+                       (f32_to_stored<ENC>(v.z, mi, den, ovf) << 16) | (f32_to_stored<ENC>(v.w, mi, den, ovf) << 24);
+            }
+        }
+        ((uint4*)out)[c] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    for (size_t i = n_vec * EPL + t; i < n; i += stride) {
+        const unsigned v = f32_to_stored<ENC>(in[i], mi, den, ovf);
+        if (ENC == ENC_F16) ((unsigned short*)out)[i] = (unsigned short)v;
+        else ((unsigned char*)out)[i] = (unsigned char)v;
+    }
+    if (ENC == ENC_F16 && overflow) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ovf += __shfl_xor(ovf, o, 64);
+        if (threadIdx.x == 0 && ovf) atomicAdd(overflow, (unsigned long long)ovf);
+    }
+}
+
+hipError_t launch_encode(const float* in, int enc, size_t n, float mi, float ma, void* out, unsigned long long* overflow,
+                         hipStream_t s) {
+    const size_t item = encoded_itemsize(enc);
+    if (item == 0 || ((uintptr_t)in & 3) || ((uintptr_t)out & (item - 1)) || ((uintptr_t)overflow & 7)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    // (a stack section or a tensor view may be 4-byte aligned only: then every pixel goes through the scalar loop)
+    const size_t n_vec = (((uintptr_t)in | (uintptr_t)out) & 15) ? 0 : n / (16 / item);
+    const size_t work = std::max(n_vec, n - n_vec * (16 / item));     // threads the longer of the two loops can use
+    const int blocks = (int)std::min<size_t>((work + 63) / 64, 32768);
+    if (enc == ENC_F16)
+        hipLaunchKernelGGL(encode_kernel<ENC_F16>, dim3(blocks), dim3(64), 0, s, in, out, n_vec, n, 0.0f, 1.0f, overflow);
+    else
+        hipLaunchKernelGGL(encode_kernel<ENC_U8>, dim3(blocks), dim3(64), 0, s, in, out, n_vec, n, mi, ma - mi, nullptr);
+    return hipGetLastError();
+}
+
 // y[z][y][x] (dense) = x_view[z][y][x]*p[0] + p[1] with p on the device: the (x - mu)/std step of
 // Denoise._denoise (denoise.py:284) applied to a (strided) patch view before the network reads it.
 __global__ __launch_bounds__(256) void affine_dev_kernel(const float* __restrict__ x, int D, int H, int W,

@@ -25,6 +25,8 @@ tpz_stage::Slot* stage_slot(tpz_stage* st, int slot) {
 
 // tpz_stage_h2d_decode: the stored pixels of an n-pixel image lie behind its fp32 form, at the next multiple of 256 bytes
 size_t stage_raw_offset(size_t n) { return (4 * n + 255) & ~(size_t)255; }
+// tpz_stage_d2h_encode: the 8-byte overflow counter of a result lies behind its encoded pixels, at the next multiple of 256 bytes
+size_t stage_counter_offset(size_t pixel_bytes) { return (pixel_bytes + 255) & ~(size_t)255; }
 
 // host-pointer entry points: two slots of the ctx's own ring (input, output), grown on demand
 int io_stage(tpz_ctx* ctx, size_t bytes, tpz_stage** out) {
@@ -136,6 +138,39 @@ int tpz_stage_d2h(tpz_stage* st, int slot, const void* d_src, size_t bytes) {
     HIPCHK(ctx, hipEventRecord(sl->produced, ctx->stream));           // everything queued so far produced d_src
     HIPCHK(ctx, hipStreamWaitEvent(st->copy, sl->produced, 0));
     HIPCHK(ctx, hipMemcpyAsync(sl->h, d_src, bytes, hipMemcpyDeviceToHost, st->copy));
+    HIPCHK(ctx, hipEventRecord(sl->ready, st->copy));
+    return 0;
+}
+size_t tpz_stage_encode_bytes(int enc, size_t n) {
+    const size_t item = encoded_itemsize(enc);
+    if (item == 0 || n > ((size_t)1 << 60)) return 0;
+    return stage_counter_offset(n * item) + 256;
+}
+int tpz_stage_d2h_encode(tpz_stage* st, int slot, const float* d_src, size_t n, int enc, const float* params) {
+    auto* sl = stage_slot(st, slot);
+    tpz_ctx* ctx = st ? st->ctx : nullptr;
+    if (!sl || !d_src) return fail(ctx, "tpz_stage_d2h_encode: bad slot or NULL source");
+    const size_t item = encoded_itemsize(enc), need = tpz_stage_encode_bytes(enc, n);
+    if (item == 0) return fail(ctx, "tpz_stage_d2h_encode: encoding %d is neither TPZ_ENC_F16 nor TPZ_ENC_U8", enc);
+    if (enc == ENC_U8 && !params) return fail(ctx, "tpz_stage_d2h_encode: TPZ_ENC_U8 needs params = {mi, ma}");
+    if (need == 0 || need > st->slot_bytes)
+        return fail(ctx, "tpz_stage_d2h_encode: %zu pixels of encoding %d need a slot of %zu bytes, this ring has %zu", n, enc, need,
+                    st->slot_bytes);
+    if (((uintptr_t)d_src & 3) || ((const char*)d_src < (const char*)sl->d + st->slot_bytes &&
+                                   (const char*)d_src + 4 * n > (const char*)sl->d))
+        return fail(ctx, "tpz_stage_d2h_encode: d_src must be 4-byte aligned and lie outside the slot's device buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // encoded pixels at the start of the slot's device buffer, the overflow counter behind them; the encode runs on the copy
+    // stream, between the `produced` event and the copy, so `ready` means: encoded pixels and counter are in the pinned slot
+    const size_t off = stage_counter_offset(n * item);
+    unsigned long long* d_count = (unsigned long long*)((char*)sl->d + off);
+    const float mi = enc == ENC_U8 ? params[0] : 0.0f, ma = enc == ENC_U8 ? params[1] : 1.0f;
+    HIPCHK(ctx, hipEventRecord(sl->produced, ctx->stream));           // everything queued so far produced d_src
+    HIPCHK(ctx, hipStreamWaitEvent(st->copy, sl->produced, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(st->copy, sl->released, 0));      // kernels of the slot's previous use are done
+    HIPCHK(ctx, hipMemsetAsync(d_count, 0, 8, st->copy));
+    HIPCHK(ctx, launch_encode(d_src, enc, n, mi, ma, sl->d, d_count, st->copy));
+    HIPCHK(ctx, hipMemcpyAsync(sl->h, sl->d, off + 8, hipMemcpyDeviceToHost, st->copy));
     HIPCHK(ctx, hipEventRecord(sl->ready, st->copy));
     return 0;
 }

@@ -161,3 +161,19 @@ int tpz_decode(tpz_ctx* ctx, const void* d_raw, int mrc_mode, size_t n, float* d
                         [=](hipStream_t st) { return launch_decode(d_raw, mrc_mode, n, d_out, st); }));
     return 0;
 }
+
+int tpz_encode(tpz_ctx* ctx, const float* d_in, size_t n, int enc, const float* params, void* d_out,
+               unsigned long long* d_overflow) {
+    if (!ctx || !d_in || !d_out) return fail(ctx, "tpz_encode: bad arguments");
+    const size_t item = encoded_itemsize(enc);
+    if (item == 0) return fail(ctx, "tpz_encode: encoding %d is neither TPZ_ENC_F16 nor TPZ_ENC_U8", enc);
+    if (enc == ENC_U8 && !params) return fail(ctx, "tpz_encode: TPZ_ENC_U8 needs params = {mi, ma}");
+    if (n == 0) return 0;
+    if (((uintptr_t)d_in & 3) || ((uintptr_t)d_out & (item - 1)) || ((uintptr_t)d_overflow & 7))
+        return fail(ctx, "tpz_encode: d_in must be 4-byte aligned, d_out aligned to its pixel, d_overflow 8-byte");
+    const float mi = enc == ENC_U8 ? params[0] : 0.0f, ma = enc == ENC_U8 ? params[1] : 1.0f;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, enqueue(ctx, 2, 0.0, nullptr, (double)n * (item + 4),
+                        [=](hipStream_t st) { return launch_encode(d_in, enc, n, mi, ma, d_out, d_overflow, st); }));
+    return 0;
+}

@@ -106,11 +106,13 @@ class Denoise3D(Denoise):
         super().__init__(model, use_cuda, dims=3)
 
     def denoise(self, tomo: np.ndarray, patch_size: int = 96, padding: int = 48, batch_size: int = 1,
-                volume_num: int = 1, total_volumes: int = 1, verbose: bool = True, across_ranks: bool = False) -> np.ndarray:
+                volume_num: int = 1, total_volumes: int = 1, verbose: bool = True, across_ranks: bool = False,
+                stored: Optional[dict] = None) -> np.ndarray:
         """across_ranks=True (multi-process launch, every rank holding the same tomogram): the ceil(n / patch)^3 tiles are
         dealt round-robin to the ranks -- they are independent (datasets.py:412-468), the global mean / std every rank
         computes over the whole volume is the same deterministic reduction -- and the ranks' partial volumes are summed onto
-        rank 0 with one RCCL reduce; the other ranks return None."""
+        rank 0 with one RCCL reduce; the other ranks return None.  stored: a dict that receives the float16 form of the result,
+        encoded on the resident volume before the download (tpz_encode) -- 'half', and 'lost', the finite voxels stored as inf."""
         x = self._to_device(tomo)
         dm = self.model.device_model
         if across_ranks and patch_size >= 1:
@@ -127,6 +129,9 @@ class Denoise3D(Denoise):
         if verbose:
             print(f'# [{volume_num}/{total_volumes}] 100%', file=sys.stderr, end='\r')
             print(' ' * 100, file=sys.stderr, end='\r')
+        if stored is not None:
+            half, stored['lost'] = rt.encode(y, rt.ENC_F16, ctx=dm.ctx)
+            stored['half'] = half.cpu().numpy()
         if torch.is_tensor(tomo) and tomo.is_cuda:                # (a volume decoded on the device: _tomogram_io)
             return y.cpu().numpy()
         return y.cpu().numpy().astype(np.asarray(tomo).dtype, copy=False)
@@ -370,9 +375,18 @@ def _run_jobs(jobs: List[_Job], read, process, write, progress) -> list:
 def denoise_stack(path: str, output_path: str, models: List[Denoise], lowpass: float = 1, pixel_cutoff: float = 0,
                   gaus=None, inv_gaus=None, deconvolve: bool = True, deconv_patch: int = 1, patch_size: int = 1024,
                   padding: int = 500, normalize: bool = True, use_cuda: bool = True):
+    """the reference's signature (denoise.py:419-447) around denoise_stack_stored: a float32 output stack"""
+    return denoise_stack_stored(path, output_path, models, lowpass, pixel_cutoff, gaus, inv_gaus, deconvolve, deconv_patch,
+                                patch_size, padding, normalize, use_cuda, float16=False)
+
+
+def denoise_stack_stored(path: str, output_path: str, models: List[Denoise], lowpass: float = 1, pixel_cutoff: float = 0,
+                         gaus=None, inv_gaus=None, deconvolve: bool = True, deconv_patch: int = 1, patch_size: int = 1024,
+                         padding: int = 500, normalize: bool = True, use_cuda: bool = True, *, float16: bool = False):
     """every section of one MRC stack, written back as one stack with the input's header.  On the device (runs_on_device) the
     sections go through the ring of denoise_stream, each with its own statistics, and rank r of a multi-process launch takes
-    sections r, r + world, ... -- all ranks write the one output file (_denoise_stack_device); otherwise the host loop."""
+    sections r, r + world, ... -- all ranks write the one output file (_denoise_stack_device); otherwise the host loop.
+    float16: the output stack is stored as float16 (MRC mode 12)."""
     from . import mrc
     with open(path, 'rb') as f:
         stack, header, extended_header = mrc.parse(f.read())
@@ -380,8 +394,8 @@ def denoise_stack(path: str, output_path: str, models: List[Denoise], lowpass: f
     models = models or []
     if stack.dtype.kind in 'iuf' and runs_on_device(models, lowpass, pixel_cutoff, gaus, inv_gaus, deconvolve):
         return _denoise_stack_device(stack, header, extended_header, output_path, models, patch_size, padding, normalize,
-                                     lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch, cutoff=pixel_cutoff,
-                                     gaus=gaus, inv_gaus=inv_gaus)
+                                     float16=float16, lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch,
+                                     cutoff=pixel_cutoff, gaus=gaus, inv_gaus=inv_gaus)
     out = np.zeros_like(stack)
     for k, section in enumerate(stack):
         out[k] = denoise_image(section, models, lowpass=lowpass, cutoff=pixel_cutoff, gaus=gaus, inv_gaus=inv_gaus,
@@ -391,19 +405,24 @@ def denoise_stack(path: str, output_path: str, models: List[Denoise], lowpass: f
     print('', file=sys.stderr)
     print('# writing to', output_path, file=sys.stderr)
     with open(output_path, 'wb') as f:
-        mrc.write(f, out, header=header, extended_header=extended_header)
+        if float16:
+            mrc.write(f, streaming.as_float16(out, output_path), header=header, extended_header=extended_header, dtype=np.float16)
+        else:
+            mrc.write(f, out, header=header, extended_header=extended_header)
     return out
 
 
 def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc', suffix: str = '',
                    models: List[Denoise] = None, lowpass: float = 1, pixel_cutoff: float = 0, gaus=None, inv_gaus=None,
                    deconvolve: bool = True, deconv_patch: int = 1, patch_size: int = 1024, padding: int = 500,
-                   normalize: bool = True, use_cuda: bool = True, return_images: bool = True):
+                   normalize: bool = True, use_cuda: bool = True, return_images: bool = True, float16: bool = False):
     """one output image per micrograph; rank r of a multi-process launch takes micrographs r, r + world, ...
+    float16 (format 'mrc' only): the files are stored as float16 (MRC mode 12), encoded on the device.
     Returns the denoised micrographs like the reference (denoise.py:450-490 keeps every one of them in memory);
     return_images=False (the CLI, which ignores them) returns the output paths instead."""
-    from . import parallel
+    from . import mrc, parallel
     from .utils.image import load_image, save_image
+    mrc.check_float16_formats(float16, [format])
     rank, _, world = parallel.init_from_env()
     if output_path:
         os.makedirs(output_path, exist_ok=True)
@@ -415,7 +434,7 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
     # pass-through), keeps the host loop
     if runs_on_device(models, lowpass, pixel_cutoff, gaus, inv_gaus, deconvolve):
         return _denoise_stream_device(jobs, models, patch_size, padding, normalize, len(micrographs), return_images,
-                                      lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch, cutoff=pixel_cutoff,
+                                      float16=float16, lowpass=lowpass, deconvolve=deconvolve, deconv_patch=deconv_patch, cutoff=pixel_cutoff,
                                       gaus=gaus, inv_gaus=inv_gaus)
 
     def read(job):
@@ -428,7 +447,7 @@ def denoise_stream(micrographs: List[str], output_path: str, format: str = 'mrc'
                              normalize=normalize, use_cuda=use_cuda)
 
     def write(job, item, mic):
-        save_image(mic, job.dst, header=item[1], extended_header=item[2])
+        save_image(streaming.as_float16(mic, job.dst) if float16 else mic, job.dst, header=item[1], extended_header=item[2])
 
     total = len(micrographs)
     out = _run_jobs(jobs, read, process, write, lambda n: print(f'# {n} of {total} completed.', file=sys.stderr, end='\r'))
@@ -448,36 +467,45 @@ def runs_on_device(models, lowpass: float = 1, pixel_cutoff: float = 0, gaus=Non
 RING_MIN_BYTES = 1 << 20
 
 
-def stack_section_offset(k: int, ny: int, nx: int, extended_bytes: int) -> int:
-    """byte of section k in an MRC stack as mrc.write lays it out: the 1024-byte header, the extended header, float32 sections"""
-    return 1024 + extended_bytes + 4 * k * ny * nx
+def stack_section_offset(k: int, ny: int, nx: int, extended_bytes: int, itemsize: int = 4) -> int:
+    """byte of section k in an MRC stack as mrc.write lays it out: the 1024-byte header, the extended header, sections of float32
+    pixels (itemsize 4) or, under --float16, of float16 pixels (itemsize 2)"""
+    return 1024 + extended_bytes + itemsize * k * ny * nx
 
 
 def _denoise_stream_device(jobs: List[_Job], models: List[Denoise], patch_size: int, padding: int, normalize: bool, total: int,
-                           return_images: bool = False, **options) -> list:
+                           return_images: bool = False, float16: bool = False, **options) -> list:
     """the `topaz denoise` loop with every pass over the pixels on the device (_device_ring); options: the keyword arguments of
-    denoise_image_device (lowpass, deconvolve, deconv_patch, cutoff, gaus, inv_gaus)"""
+    denoise_image_device (lowpass, deconvolve, deconv_patch, cutoff, gaus, inv_gaus).  The result leaves the device in the type
+    its file stores: float16 under `float16`, the uint8 of save_image's quantize for a PNG / JPEG file nobody asked back as an
+    image, float32 otherwise."""
+    from .stats import EIGHT_BIT_FORMATS
     from .utils.image import save_image
     results = [job.dst for job in jobs]
+    eight_bit = bool(jobs) and os.path.splitext(jobs[0].dst)[1][1:] in EIGHT_BIT_FORMATS and not return_images
+    encode = rt.ENC_F16 if float16 else (rt.ENC_U8, (-3, 3)) if eight_bit else None
 
     def emit(host, n, path, header, extended):
         save_image(host, jobs[n].dst, header=header, extended_header=extended)
         if return_images:
-            results[n] = np.array(host, copy=True)
+            results[n] = np.array(host, dtype=np.float32)
 
     _device_ring([job.src for job in jobs], models, lambda x: denoise_image_device(x, models, patch_size, padding, normalize,
-                                                                                   **options), emit, total)
+                                                                                   **options), emit, total, encode,
+                 lambda lost, n, *_: streaming.warn_overflow(jobs[n].dst, lost))
     return results
 
 
 def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_path: str, models: List[Denoise], patch_size: int,
-                          padding: int, normalize: bool, **options) -> np.ndarray:
+                          padding: int, normalize: bool, float16: bool = False, **options) -> np.ndarray:
     """`topaz denoise --stack` through the ring of the stream: section k+1 uploads and section k-1 leaves under the kernels of
     section k, each section with its own statistics (sections below RING_MIN_BYTES run one by one on the calling thread
     instead, through the same functions).  The writer thread casts a section to the stack's dtype (what the host
     loop's np.zeros_like(stack) does to an integer stack) and puts its float32 form at its byte of the output file (os.pwrite).
     Rank r of a multi-process launch takes sections r, r + world, ...; rank 0 lays down the header, and a barrier makes the file
-    whole before any rank returns.  Returns the full stack (one process) or this rank's sections in a zero array."""
+    whole before any rank returns.  Returns the full stack (one process) or this rank's sections in a zero array.
+    float16: the header says mode 12 and a section takes 2 bytes per pixel; a section of a float stack is encoded on the device
+    (an integer stack's is truncated on the host first, as ever, and converted there)."""
     from . import mrc, parallel
     rank, local_rank, world = parallel.init_from_env()
     extended_header = extended_header or b''
@@ -485,30 +513,42 @@ def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_pat
     nz, ny, nx = sections.shape
     mine = parallel.shard_indices(nz, rank, world)
     out = np.zeros_like(sections)
+    itemsize, stored = (2, np.float16) if float16 else (4, np.float32)
+    encode = rt.ENC_F16 if float16 and stack.dtype.kind == 'f' else None
     print(f'# rank {rank} of {world}: stack sections {mine} of {nz}, writing to {output_path}', file=sys.stderr, flush=True)
     fd = os.open(output_path, os.O_WRONLY | os.O_CREAT, 0o666)     # every rank opens the one file, none empties it
     try:
         if rank == 0:
             # (the header mrc.write gives a stack written with the input's header; the length fixed up front cuts off what a
             # longer file of an earlier run would leave behind)
-            os.pwrite(fd, mrc.header_struct.pack(*list(header._replace(mode=2))) + extended_header, 0)
-            os.ftruncate(fd, stack_section_offset(nz, ny, nx, len(extended_header)))
+            os.pwrite(fd, mrc.header_struct.pack(*list(header._replace(mode=mrc.get_mode_for_header(stored)))) + extended_header, 0)
+            os.ftruncate(fd, stack_section_offset(nz, ny, nx, len(extended_header), itemsize))
+
+        def overflowed(lost, n, k, *_):
+            streaming.warn_overflow(f'{output_path} section {k}', lost)
 
         def emit(host, n, k, _header, _extended):
             out[k] = host                                       # the cast to the stack's dtype (truncation for integers)
-            streaming.pwrite_all(fd, np.ascontiguousarray(out[k], dtype=np.float32),
-                                 stack_section_offset(k, ny, nx, len(extended_header)))
+            if encode is None:                                  # (an encoded section is written as it came down)
+                host = streaming.as_float16(out[k], f'{output_path} section {k}') if float16 else \
+                    np.ascontiguousarray(out[k], dtype=np.float32)
+            streaming.pwrite_all(fd, host, stack_section_offset(k, ny, nx, len(extended_header), itemsize))
 
         def process(x):
             return denoise_image_device(x, models, patch_size, padding, normalize, **options)
 
         if 4 * ny * nx >= RING_MIN_BYTES:
-            _device_ring([(k, sections[k], None, None) for k in mine], models, process, emit, nz)
+            _device_ring([(k, sections[k], None, None) for k in mine], models, process, emit, nz, encode, overflowed)
         else:
             # small sections: the copies the ring would hide are shorter than its hand-offs between threads
             ctx = models[0].model.device_model.ctx if models else rt.get_context()
             for n, k in enumerate(mine):
-                emit(process(rt.as_device_f32(np.array(sections[k], dtype=np.float32), ctx)).cpu().numpy(), n, k, None, None)
+                y = process(rt.as_device_f32(np.array(sections[k], dtype=np.float32), ctx))
+                if encode is not None:
+                    y, lost = rt.encode(y, encode, ctx=ctx)
+                    if lost:
+                        overflowed(lost, n, k)
+                emit(y.cpu().numpy(), n, k, None, None)
                 print(f'# {n + 1} of {nz} completed.', file=sys.stderr, end='\r')
             print('', file=sys.stderr)
     finally:
@@ -518,11 +558,12 @@ def _denoise_stack_device(stack: np.ndarray, header, extended_header, output_pat
     return out.reshape(stack.shape)
 
 
-def _device_ring(items: list, models: List[Denoise], process, emit, total: int) -> None:
+def _device_ring(items: list, models: List[Denoise], process, emit, total: int, encode=None, on_overflow=None) -> None:
     """The device-resident loop shared by the stream and the stack (streaming.stream_images).  items: file paths, or (key, array,
     header, extended header) for images already in memory.  The GPU runs process(device tensor) -> device tensor on image i
     while image i+1 is decoded and uploaded, and a writer thread calls emit(pinned host array, i, path or key, header, extended
-    header) for image i-1."""
+    header) for image i-1.  encode: the type the results leave the device in (streaming.ResultRing.put), on_overflow(count, i,
+    path or key, header, extended header): the ring's hook."""
     if not items:
         return
     ctx = models[0].model.device_model.ctx if models else rt.get_context()
@@ -531,13 +572,13 @@ def _device_ring(items: list, models: List[Denoise], process, emit, total: int) 
     def step(key, x, header, extended):
         n, y = next(count), process(x)
         print(f'# {n + 1} of {total} completed.', file=sys.stderr, end='\r')
-        return y, (n, key, header, extended)
+        return streaming.Put(y, (n, key, header, extended), encode)
 
-    streaming.stream_images(items, ctx, step, emit)
+    streaming.stream_images(items, ctx, step, emit, on_overflow=on_overflow)
     print('', file=sys.stderr)
 
 
-def _tomogram_io():
+def _tomogram_io(float16: bool = False):
     from . import mrc
 
     def read(job):
@@ -550,11 +591,17 @@ def _tomogram_io():
             tomo, header, extended = mrc.parse(f.read())
         return tomo.astype(np.float32), header, extended
 
-    def write(job, item, denoised):
-        # 3-D denoise refreshes the density statistics of the header (denoise.py:523-526)
+    def write(job, item, denoised, stored=None):
+        # 3-D denoise refreshes the density statistics of the header (denoise.py:523-526); under float16 they stay those of the
+        # float32 volume, whose float16 form (Denoise3D.denoise's `stored`) is what the file holds
         header = item[1]._replace(mode=2, amin=denoised.min(), amax=denoised.max(), amean=denoised.mean())
         with open(job.dst, 'wb') as f:
-            mrc.write(f, denoised, header=header, extended_header=item[2])
+            if float16:
+                if stored['lost']:
+                    streaming.warn_overflow(job.dst, stored['lost'])
+                mrc.write(f, stored['half'], header=header, extended_header=item[2], dtype=np.float16)
+            else:
+                mrc.write(f, denoised, header=header, extended_header=item[2])
     return read, write
 
 
@@ -573,25 +620,28 @@ def _resolved(volume):
 
 
 def denoise_tomogram(path: str, model: Denoise3D, outdir: str = None, suffix: str = '', patch_size: int = 96,
-                     padding: int = 48, volume_num: int = 1, total_volumes: int = 1, gaus=None, verbose: bool = True):
+                     padding: int = 48, volume_num: int = 1, total_volumes: int = 1, gaus=None, verbose: bool = True,
+                     float16: bool = False):
     """one tomogram; returns the INPUT volume, Gaussian-filtered when `gaus` is given -- what the reference returns
     (it filters `tomo`, writes `denoised`: denoise.py:509,528-530)"""
-    read, write = _tomogram_io()
+    read, write = _tomogram_io(float16)
+    stored = {} if float16 else None
     job = _Job(0, path, _output_path(path, outdir, suffix, os.path.splitext(path)[1]))
     from concurrent.futures import ThreadPoolExecutor
     item = read(job)
     with ThreadPoolExecutor(1, 'tpz-f32') as pool:
         x, volume = _tomogram_device(model, item[0], pool)
         denoised = model.denoise(x, patch_size=patch_size, padding=padding, batch_size=1, volume_num=volume_num,
-                                 total_volumes=total_volumes, verbose=verbose)
+                                 total_volumes=total_volumes, verbose=verbose, stored=stored)
         del x
-        write(job, item, denoised)
+        write(job, item, denoised, stored)
         volume = _resolved(volume)
     return gaus.apply(volume) if gaus is not None else volume
 
 
 def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: str, suffix: str = '', gaus: float = None,
-                            patch_size: int = 96, padding: int = 48, verbose: bool = True, use_cuda: bool = True):
+                            patch_size: int = 96, padding: int = 48, verbose: bool = True, use_cuda: bool = True,
+                            float16: bool = False):
     """tomograms (or, when there are fewer tomograms than ranks, their tiles) sharded over the ranks of a multi-process
     launch; the next volume is read while this one is denoised"""
     from . import parallel
@@ -604,7 +654,7 @@ def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: s
     rank, _, world = parallel.init_from_env()
     if output_path:
         os.makedirs(output_path, exist_ok=True)
-    read, write = _tomogram_io()
+    read, write_volume = _tomogram_io(float16)
     total = len(volumes)
     # fewer tomograms than ranks: split each tomogram's TILES over all ranks instead of leaving ranks idle (a 512x512x256
     # volume is 108 independent 192^3 tiles); otherwise whole tomograms are dealt to the ranks
@@ -619,15 +669,13 @@ def denoise_tomogram_stream(volumes: List[str], model: Denoise3D, output_path: s
     def process(job, item):
         x, volume = _tomogram_device(model, item[0], pool)
         inputs.append(volume)
+        stored = {} if float16 else None
         return model.denoise(x, patch_size=patch_size, padding=padding, batch_size=1, volume_num=job.index + 1,
-                             total_volumes=total, verbose=verbose and rank == 0, across_ranks=by_tiles)
+                             total_volumes=total, verbose=verbose and rank == 0, across_ranks=by_tiles, stored=stored), stored
 
-    if by_tiles:
-        plain_write = write
-
-        def write(job, item, denoised):            # only rank 0 holds the assembled volume
-            if denoised is not None:
-                plain_write(job, item, denoised)
+    def write(job, item, result):                  # (sharded by tiles, only rank 0 holds the assembled volume)
+        if result[0] is not None:
+            write_volume(job, item, *result)
 
     try:
         _run_jobs(jobs, read, process, write, lambda n: print(f'# {n} of {total} tomograms denoised.', file=sys.stderr, end='\r'))

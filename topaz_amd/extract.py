@@ -354,7 +354,8 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
                       patch_size, only_validate: bool, output: str, per_micrograph: bool, suffix: str, out_format: str,
                       up_scale: float, down_scale: float, dims=2, verbose: bool = False, precision_check: str = 'never',
                       preprocess=None, particle_stack: Optional[str] = None, particle_size: Optional[int] = None,
-                      particle_resize: int = -1, particle_threshold: float = -np.inf, particle_metadata: Optional[str] = None):
+                      particle_resize: int = -1, particle_threshold: float = -np.inf, particle_metadata: Optional[str] = None,
+                      particle_float16: bool = False):
     """preprocess: None, or a callable device tensor -> device tensor (stats.DevicePreprocess) every micrograph goes through
     before it is scored (`--preprocess`).  Everything downstream -- patches, the radius search, the ranks, the outputs -- sees
     the smaller, normalised image only: picks are in ITS frame, as they are when `topaz preprocess` wrote it to a file first;
@@ -362,7 +363,8 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
     particle_stack: also write the MRC particle stack (and its STAR file) `topaz particle_stack` would make of the pick table:
     particle_size boxes (particle_resize: down-sampled to that size) around the picks with score >= particle_threshold, cut at
     the coordinates the table holds from the image the feed decoded -- under `preprocess` the raw frame -- while it is resident
-    (utils.picks.ExtractStack).  The pick table itself is what it is without the stack."""
+    (utils.picks.ExtractStack); particle_float16: stored as float16 (MRC mode 12).  The pick table itself is what it is without
+    the stack."""
     from .utils import picks as pk
     check_preprocess_args(preprocess, model, dims)               # (before anything is loaded)
     pk.check_particle_stack_args(particle_stack, particle_size, particle_resize, model, dims, targets, only_validate)
@@ -383,7 +385,7 @@ def extract_particles(paths: List[str], model, device: int, batch_size: int, thr
     if particle_stack:
         pk.check_particle_stack_inputs(paths)                    # (still nothing loaded)
         stack = pk.ExtractStack(particle_stack, particle_size, particle_resize, particle_threshold, particle_metadata,
-                                (rank, local_rank, world))
+                                (rank, local_rank, world), float16=particle_float16)
     mine = parallel.shard_indices(len(paths), rank, world)
     maps = score_images(model, [paths[i] for i in mine], device=device, patch_size=patch_size, batch_size=batch_size,
                         keep_on_device=True, precision_check=precision_check, verbose=verbose, preprocess=preprocess,

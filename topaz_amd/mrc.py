@@ -3,7 +3,8 @@
 
 Header: one native-endian C struct of exactly 1024 bytes; the image follows the `next` bytes of
 extended header; modes 0/1/2/3/4/6/12/16; data is `nz*ny*nx` elements in C order, squeezed to 2-D
-when nz == 1; `write` always stores float32 and forces mode 2 on a supplied header.
+when nz == 1; `write` stores float32 and forces mode 2 on a supplied header, or, asked for dtype=np.float16, stores the float16
+array it is given under mode 12.
 """
 from __future__ import annotations
 
@@ -42,6 +43,8 @@ def get_mode_from_header(header):
 
 
 def get_mode_for_header(dtype):
+    if np.dtype(dtype) == np.float16:           # asked for by name (the search below keeps skipping it, as the reference's does)
+        return 12
     for mode, dt in _MODE_TO_DTYPE.items():
         if mode != 12 and np.dtype(dtype) == np.dtype(dt):
             return mode
@@ -91,6 +94,14 @@ def read_into(path: str, alloc):
 STORED_MODES = {np.dtype(np.int8): 0, np.dtype(np.int16): 1, np.dtype(np.uint16): 6, np.dtype(np.float16): 12}
 
 
+def check_float16_formats(float16: bool, formats) -> None:
+    """float16 output is a property of MRC files (mode 12): asked for together with any other output format it is refused --
+    by the commands before anything is read (`--float16` with `--format png`)"""
+    other = [f for f in formats if f != 'mrc']
+    if float16 and other:
+        raise ValueError(f'--float16 stores MRC mode 12 and goes with --format mrc only, not {",".join(other)}')
+
+
 def read_stored_into(path: str, alloc):
     """read_into without the conversion: the pixels of an MRC file of mode 0, 1, 6 or 12 are read INTO the array
     `alloc(shape, dtype)` returns, in the dtype the file stores them in (int8, int16, uint16, float16) -- one copy from the page
@@ -123,15 +134,22 @@ def make_header(shape, cella, cellb, mz=1, dtype=np.float32, order=(1, 2, 3), dm
                      b'\x00' * 4, b'\x00' * 4, rms, 0, b'\x00' * 800)
 
 
-def write(f, array, header=None, extended_header=b'', ax=1, ay=1, az=1, alpha=0, beta=0, gamma=0):
-    array = np.ascontiguousarray(array, dtype=np.float32)          # (no copy when it already is)
+def write(f, array, header=None, extended_header=b'', ax=1, ay=1, az=1, alpha=0, beta=0, gamma=0, dtype=np.float32):
+    """dtype: np.float32 (mode 2) or np.float16 (mode 12) -- the type the pixels are stored in; the array is cast to it (a float16
+    array under dtype=np.float16 is stored as given).  A generated header describes the file: under float16 its density
+    statistics are those of the stored values, taken in float32.  A supplied header keeps its statistics; only its mode follows."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError('mrc.write stores float32 (mode 2) or float16 (mode 12), not ' + str(dtype))
+    array = np.ascontiguousarray(array, dtype=dtype)               # (no copy when it already is)
     if extended_header is None:
         extended_header = b''
     if header is None:
-        header = make_header(array.shape, (ax, ay, az), (alpha, beta, gamma), mz=1, dmin=array.min(), dmax=array.max(),
-                             dmean=array.mean(), rms=array.std(), exthd_size=len(extended_header))
+        values = array if dtype == np.float32 else array.astype(np.float32)
+        header = make_header(array.shape, (ax, ay, az), (alpha, beta, gamma), mz=1, dtype=dtype, dmin=values.min(),
+                             dmax=values.max(), dmean=values.mean(), rms=values.std(), exthd_size=len(extended_header))
     else:
-        header = header._replace(mode=2)          # only the mode is refreshed (mrc.py:231-232)
+        header = header._replace(mode=get_mode_for_header(dtype))  # only the mode is refreshed (mrc.py:231-232)
     f.write(header_struct.pack(*list(header)))
     f.write(extended_header)
     f.write(memoryview(array.reshape(-1)).cast('B'))               # (the array's own memory: no tobytes() copy)

@@ -21,6 +21,10 @@ _contexts = {}
 # This is the one place it lives; it is read when a check runs.
 DEFAULT_BAR = 1e-4
 
+# The encodings a float32 result can leave the device in (tpz_encode, Stage.download_encoded) and the dtype each is stored as
+ENC_F16, ENC_U8 = _lib.TPZ_ENC_F16, _lib.TPZ_ENC_U8
+ENC_DTYPES = {ENC_F16: np.dtype(np.float16), ENC_U8: np.dtype(np.uint8)}
+
 
 class Context:
     """tpz_ctx for one device.  Use get_context(device) rather than constructing directly."""
@@ -256,6 +260,30 @@ class Stage:
 
     def download(self, slot: int, src: torch.Tensor) -> None:
         check(self.ctx.lib.tpz_stage_d2h(self.handle, slot, _ptr(src), src.numel() * src.element_size()), self.ctx.handle)
+
+    @staticmethod
+    def encode_bytes(ctx: Context, enc: int, n: int) -> int:
+        """bytes a slot needs for download_encoded of n pixels: the encoded pixels and, behind them, the overflow counter"""
+        need = int(ctx.lib.tpz_stage_encode_bytes(int(enc), int(n)))
+        if need == 0:
+            raise _lib.TopazHipError(f'encoding {enc} is neither ENC_F16 nor ENC_U8')
+        return need
+
+    def download_encoded(self, slot: int, src: torch.Tensor, enc: int, params=None) -> None:
+        """download() of a float32 tensor in the type a file stores it in (tpz_stage_d2h_encode): ENC_F16, the float16 of numpy's
+        astype, or ENC_U8 with params = (mi, ma), the uint8 of utils.image.quantize.  The pixels are encoded on the copy stream
+        and 2 or 1 bytes per pixel cross to the pinned slot; after wait(), host_array(slot, shape, ENC_DTYPES[enc]) holds them
+        and overflow_count(slot, n, enc) the number of finite values float16 stored as +-inf."""
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            raise _lib.TopazHipError('download_encoded: a contiguous float32 tensor is needed')
+        p = None if params is None else (C.c_float * 2)(float(params[0]), float(params[1]))
+        check(self.ctx.lib.tpz_stage_d2h_encode(self.handle, slot, _ptr(src), src.numel(), int(enc), p), self.ctx.handle)
+
+    def overflow_count(self, slot: int, n: int, enc: int) -> int:
+        """the counter download_encoded left behind the n encoded pixels of the slot (read it after wait())"""
+        off = self.encode_bytes(self.ctx, enc, n) - 256
+        p = self.ctx.lib.tpz_stage_host_ptr(self.handle, slot)
+        return int(C.c_ulonglong.from_address(p + off).value)
 
     def wait(self, slot: int) -> None:
         check(self.ctx.lib.tpz_stage_wait(self.handle, slot), self.ctx.handle)
@@ -785,6 +813,32 @@ def decode_stored(x: np.ndarray, ctx: Optional[Context] = None) -> torch.Tensor:
     if x.size:
         check(ctx.lib.tpz_decode(ctx.handle, _ptr(raw), mode, x.size, _ptr(y)), ctx.handle)
     return y
+
+
+def encode(x: torch.Tensor, enc: int, params=None, ctx: Optional[Context] = None, count: bool = True,
+           out: Optional[torch.Tensor] = None):
+    """a float32 device tensor -> (the tensor a file stores, overflow count) on the device (tpz_encode): ENC_F16 gives the
+    float16 tensor of numpy's astype(np.float16), bit for bit, and the number of finite values stored as +-inf; ENC_U8 with
+    params = (mi, ma) the uint8 tensor of utils.image.quantize and 0.  count=False passes no counter (the count returned is
+    None); out: a tensor of the stored dtype to write into (its first x.numel() elements; views that are only 2- or 4-byte
+    aligned are fine).  x may be any contiguous float32 view."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    if enc not in ENC_DTYPES:
+        raise _lib.TopazHipError(f'encode: encoding {enc} is neither ENC_F16 nor ENC_U8')
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        x = as_device_f32(x, ctx)
+    dtype = torch.float16 if enc == ENC_F16 else torch.uint8
+    if out is None:
+        out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    elif out.dtype != dtype or out.numel() < x.numel() or not out.is_contiguous():
+        raise _lib.TopazHipError('encode: `out` must be a contiguous tensor of the stored dtype with room for every pixel')
+    counter = torch.zeros(1, dtype=torch.int64, device=x.device) if count and enc == ENC_F16 else None
+    p = None if params is None else (C.c_float * 2)(float(params[0]), float(params[1]))
+    if x.numel():
+        check(ctx.lib.tpz_encode(ctx.handle, _ptr(x), x.numel(), int(enc), p, _ptr(out), None if counter is None else _ptr(counter)),
+              ctx.handle)
+    return out, (int(counter.item()) if counter is not None else (0 if count else None))
 
 
 def normalize_cutoff(x: torch.Tensor, mean: float, std: float, cutoff: float, ctx: Optional[Context] = None) -> torch.Tensor:

@@ -15,7 +15,7 @@ from __future__ import annotations
 import json
 import os
 import sys
-from typing import List
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -233,14 +233,32 @@ class DevicePreprocess:
         return y
 
 
+EIGHT_BIT_FORMATS = ('png', 'jpg', 'jpeg')     # save_image quantises these with mi, ma = -3, 3
+
+
+class _Output(NamedTuple):
+    """what the writer of _normalize_stream needs besides the pixels of one put"""
+    path: str
+    header: object
+    extended: object
+    meta: Optional[dict]
+    formats: List[str]          # the formats written from these pixels
+    last: bool                  # the image's last put: the metadata file and the progress line follow it
+
+
 def _normalize_stream(paths: List[str], dest: str, scale: int, fit_args: dict, metadata: bool, formats: List[str],
-                      verbose: bool) -> None:
-    """the loop of `normalize_images` over this process's files: streaming.stream_images around the two halves below"""
+                      verbose: bool, float16: bool = False) -> None:
+    """the loop of `normalize_images` over this process's files: streaming.stream_images around the two halves below.  The
+    result leaves the device in the type each format stores: float32 (or float16, encoded there: `float16`) for mrc / tiff, and
+    the uint8 of save_image's quantize, made there as well, for png / jpg -- one put per stored type."""
     from . import runtime as rt
     from .utils.image import downsample_device, save_image
     if not paths:
         return
     affine = fit_args['method'] == 'affine'
+    # (--affine normalises on the host, in the writer: the image comes down as float32 and is converted there)
+    as_float = [f for f in formats if affine or f not in EIGHT_BIT_FORMATS]
+    as_bytes = [f for f in formats if f not in as_float]
 
     def process(path, x, header, extended):
         if scale > 1:
@@ -252,36 +270,53 @@ def _normalize_stream(paths: List[str], dest: str, scale: int, fit_args: dict, m
             y, meta = (x if scale > 1 else x.clone()), None
         else:
             y, meta = normalize_device(x, **fit_args)        # every RNG draw happens here, in path order
-        return y, (path, header, extended, meta)
+        # one put per stored type; the last one of an image also writes its metadata
+        puts = []
+        if as_float or not as_bytes:
+            puts.append((as_float, rt.ENC_F16 if float16 and not affine else None))
+        if as_bytes:
+            puts.append((as_bytes, (rt.ENC_U8, (-3, 3))))
+        return [streaming.Put(y, (_Output(path, header, extended, meta, fmts, k == len(puts) - 1),), encode)
+                for k, (fmts, encode) in enumerate(puts)]
 
-    def write(pixels, path, header, extended, meta):
+    def write(pixels, job):
+        path, header, extended, meta, fmts, last = job
+        name = os.path.splitext(os.path.basename(path))[0]
+        stem = os.path.join(dest, name)
         if affine:
             # --affine keeps numpy's own statistics: the (down-sampled) image came down, the per-file expressions run here,
             # under the GPU's work on the next image
             pixels, meta = normalize(pixels, **fit_args)
-        name = os.path.splitext(os.path.basename(path))[0]
-        stem = os.path.join(dest, name)
-        for fmt in formats:
+            if float16:
+                pixels = streaming.as_float16(pixels, stem + '.mrc')
+        for fmt in fmts:
             save_image(pixels, stem, f=fmt, header=header, extended_header=extended)
+        if not last:
+            return
         if metadata:
             with open(stem + '.metadata.json', 'w') as fh:
                 json.dump(_jsonable(meta), fh, indent=4)
         if verbose:
             print('# processed:', name, file=sys.stderr)
 
-    streaming.stream_images(paths, rt.get_context(), process, write)
+    def overflowed(lost, job):
+        streaming.warn_overflow(os.path.join(dest, os.path.splitext(os.path.basename(job.path))[0]) + '.mrc', lost)
+
+    streaming.stream_images(paths, rt.get_context(), process, write, on_overflow=overflowed)
 
 
 def normalize_images(paths: List[str], dest: str, num_workers: int, scale: int, affine: bool, niters: int, alpha: float,
                      beta: float, sample: int, metadata: bool, formats: List[str], use_cuda: bool = True,
-                     verbose: bool = False):
+                     verbose: bool = False, float16: bool = False):
     """stats.py:334-352 as a device-resident stream.  Rank r of a multi-process launch takes files r, r + world, ...; the ranks
     write disjoint files and exchange nothing.  With sample > 1 each rank draws the sub-samples of ITS files from its own RNG, so
     the fitted subsets depend on the number of ranks (sample = 1: the same files for any number).  `num_workers` is accepted and
-    unused: the parallelism is the reader / GPU / writer pipeline and the ranks."""
-    from . import parallel
+    unused: the parallelism is the reader / GPU / writer pipeline and the ranks.  float16: the MRC files are stored as float16
+    (mode 12), encoded on the device; only with formats == ['mrc']."""
+    from . import mrc, parallel
+    mrc.check_float16_formats(float16, formats)
     rank, _, world = parallel.init_from_env()
     os.makedirs(dest, exist_ok=True)
     mine = [paths[i] for i in parallel.shard_indices(len(paths), rank, world)]
     fit_args = dict(alpha=alpha, beta=beta, num_iters=niters, sample=sample, method='affine' if affine else 'gmm')
-    _normalize_stream(mine, dest, scale, fit_args, metadata, formats, verbose)
+    _normalize_stream(mine, dest, scale, fit_args, metadata, formats, verbose, float16)

@@ -14,8 +14,9 @@ from __future__ import annotations
 import contextlib
 import os
 import queue
+import sys
 import threading
-from typing import Iterator, List, Optional, Sequence, Tuple
+from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -36,6 +37,23 @@ def pwrite_all(fd: int, view, at: int) -> None:
     done = 0
     while done < len(view):
         done += os.pwrite(fd, view[done:], at + done)
+
+
+def warn_overflow(what, count: int) -> None:
+    """the one line a command prints when float16 output stored finite values as +-inf: `what` names the file or the section"""
+    print(f'# warning: {what}: {int(count)} finite value(s) beyond the float16 range (|x| >= 65520) stored as inf',
+          file=sys.stderr, flush=True)
+
+
+def as_float16(x: np.ndarray, what) -> np.ndarray:
+    """the float16 form of a result that is on the host already (the paths that do not go through a ring), with the warning"""
+    x = np.asarray(x)
+    with np.errstate(over='ignore'):
+        half = np.ascontiguousarray(x, dtype=np.float16)
+    lost = int(np.count_nonzero(np.isinf(half) & np.isfinite(x)))
+    if lost:
+        warn_overflow(what, lost)
+    return half
 
 
 class ImageFeed:
@@ -195,7 +213,8 @@ class ImageFeed:
 
 
 class ResultRing:
-    """Carry float32 results off the device without the calling thread waiting for a copy.  put(tensor, *payload) queues the D2H
+    """Carry float32 results off the device -- as they are, or encoded there to float16 / uint8 (put's `encode`) -- without the
+    calling thread waiting for a copy.  put(tensor, *payload) queues the D2H
     copy of a device tensor into a free pinned slot of an rt.Stage ring of `depth` slots; a writer thread waits for the copy and
     calls write(host_array, *payload) -- host_array: the slot's pinned buffer as a numpy view of the tensor's shape, valid for
     the call.  The tensor is referenced here until its copy has landed.
@@ -206,8 +225,8 @@ class ResultRing:
     of pinned memory at a time, however often the sizes rise.  tpz_stage_free synchronises the context's stream, so each growth
     costs the caller one stream synchronisation -- only when a result is larger than every result before it."""
 
-    def __init__(self, ctx: 'rt.Context', write, depth: int = 2):
-        self.ctx, self.write, self.depth = ctx, write, depth
+    def __init__(self, ctx: 'rt.Context', write, depth: int = 2, on_overflow=None):
+        self.ctx, self.write, self.depth, self.on_overflow = ctx, write, depth, on_overflow
         self.stage: Optional[rt.Stage] = None
         self.slot_bytes = 0
         self.free: 'queue.Queue' = queue.Queue()
@@ -221,11 +240,17 @@ class ResultRing:
             item = self.todo.get()
             if item is None:
                 return
-            k, shape, payload = item[:3]                        # (item[3], the tensor, lives until its copy is done)
+            k, shape, payload, enc = item[:4]                   # (item[4], the tensor, lives until its copy is done)
             try:
                 if not self.failed:
                     self.stage.wait(k)                          # the D2H of this slot has landed
-                    self.write(self.stage.host_array(k, shape), *payload)
+                    if enc is None:
+                        self.write(self.stage.host_array(k, shape), *payload)
+                    else:
+                        lost = self.stage.overflow_count(k, int(np.prod(shape)), enc)
+                        if lost and self.on_overflow is not None:
+                            self.on_overflow(lost, *payload)
+                        self.write(self.stage.host_array(k, shape, rt.ENC_DTYPES[enc]), *payload)
             except BaseException as e:                          # surfaces in the calling thread
                 self.failed.append(e)
             finally:
@@ -250,14 +275,24 @@ class ResultRing:
         for k in range(self.depth):
             self.free.put(k)
 
-    def put(self, tensor: torch.Tensor, *payload) -> None:
-        self.reserve(tensor.numel() * tensor.element_size())
+    def put(self, tensor: torch.Tensor, *payload, encode=None) -> None:
+        """encode: None (the float32 bytes), rt.ENC_F16, or (rt.ENC_U8, (mi, ma)) -- the tensor is encoded on the copy stream
+        (Stage.download_encoded), `write` gets the pinned view in the stored dtype (np.float16 / np.uint8) and, before it, the
+        ring's on_overflow(count, *payload) hears of finite values float16 stored as +-inf, when there are any"""
+        enc, params = encode if isinstance(encode, tuple) else (encode, None)
+        if enc is None:
+            self.reserve(tensor.numel() * tensor.element_size())
+        else:
+            self.reserve(rt.Stage.encode_bytes(self.ctx, enc, tensor.numel()))
         k = self.free.get()
         if self.failed:
             self.free.put(k)
             raise self.failed[0]
-        self.stage.download(k, tensor)
-        self.todo.put((k, tuple(tensor.shape), payload, tensor))
+        if enc is None:
+            self.stage.download(k, tensor)
+        else:
+            self.stage.download_encoded(k, tensor, enc, params)
+        self.todo.put((k, tuple(tensor.shape), payload, enc, tensor))
 
     def close(self) -> None:
         """wait for the last write, end the thread, free the ring (idempotent; a failure stays available to check())"""
@@ -275,15 +310,25 @@ class ResultRing:
         self.close()
 
 
-def stream_images(items: Sequence, ctx: 'rt.Context', process, write) -> None:
+class Put(NamedTuple):
+    """one result of stream_images' `process`: what ResultRing.put takes"""
+    tensor: torch.Tensor
+    payload: tuple
+    encode: object = None       # None (float32), rt.ENC_F16, or (rt.ENC_U8, (mi, ma))
+
+
+def stream_images(items: Sequence, ctx: 'rt.Context', process, write, on_overflow=None) -> None:
     """The device-resident loop over files (or over images already in memory: ImageFeed).  The feed's reader thread decodes and
     uploads image i+1, process(key, device tensor, header, extended header) -> (device tensor, payload tuple) runs on image i in
     the calling thread and in order (whatever it draws from the NumPy RNG is drawn in path order), and the ring's writer thread
-    calls write(pinned host array, *payload) for image i-1.  On the way out, also by an exception: the feed is closed (its
-    reader joined), then the ring (everything queued is written, unless a write failed), then a writer's failure is raised."""
+    calls write(pinned host array, *payload) for image i-1.  process returns that pair, or a Put (the pair and the encoding the
+    result leaves the device in; on_overflow: the ring's hook), or a list of Puts: one put each.  On the way out, also by an
+    exception: the feed is closed (its reader joined), then the ring (everything queued is written, unless a write failed), then
+    a writer's failure is raised."""
     feed = iter(ImageFeed(items, ctx, headers=True))
-    with ResultRing(ctx, write) as ring, contextlib.closing(feed):         # (left in reverse: the feed closes first)
+    with ResultRing(ctx, write, on_overflow=on_overflow) as ring, contextlib.closing(feed):   # (left in reverse: the feed first)
         for key, x, header, extended in feed:
-            y, payload = process(key, x, header, extended)
-            ring.put(y, *payload)
+            results = process(key, x, header, extended)
+            for put in (results if isinstance(results, list) else [Put(*results)]):
+                ring.put(put.tensor, *put.payload, encode=put.encode)
     ring.check()

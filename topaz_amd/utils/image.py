@@ -61,8 +61,17 @@ def load_image(path, standardize=False, make_image=True, return_header=True):
 
 
 def save_mrc(x, path, header=None, extended_header=None):
+    """a float16 array is stored as it is, under MRC mode 12; anything else as float32"""
+    x = np.asarray(x)
     with open(path, 'wb') as f:
-        mrc.write(f, np.asarray(x)[np.newaxis], header=header, extended_header=extended_header or b'')
+        mrc.write(f, x[np.newaxis], header=header, extended_header=extended_header or b'',
+                  dtype=np.float16 if x.dtype == np.float16 else np.float32)
+
+
+def _as_uint8(x, mi, ma):
+    """the 8-bit image of a PNG / JPEG file: x itself when it already is one (quantised on the device: tpz_encode), else quantize"""
+    x = np.asarray(x)
+    return x if x.dtype == np.uint8 else quantize(x, mi=mi, ma=ma)
 
 
 def save_image(x, path, mi=-3, ma=3, f=None, verbose=False, header=None, extended_header=None):
@@ -79,10 +88,10 @@ def save_image(x, path, mi=-3, ma=3, f=None, verbose=False, header=None, extende
         Image.fromarray(x).save(path, 'tiff')
     elif f == 'png':
         from PIL import Image
-        Image.fromarray(quantize(x, mi=mi, ma=ma)).save(path, 'png')
+        Image.fromarray(_as_uint8(x, mi, ma)).save(path, 'png')
     elif f in ('jpg', 'jpeg'):
         from PIL import Image
-        Image.fromarray(quantize(x, mi=mi, ma=ma)).save(path, 'jpeg')
+        Image.fromarray(_as_uint8(x, mi, ma)).save(path, 'jpeg')
 
 
 # ---- truncated-DFT downsample (topaz/utils/image.py:38-61, `topaz downsample`) --------------------------------
@@ -155,17 +164,32 @@ def downsample(x, factor=1, shape=None):
     return downsample_device(torch.from_numpy(np.ascontiguousarray(x)), factor, shape).cpu().numpy().astype(x.dtype)
 
 
-def downsample_file(path, scale, output, verbose=False):
-    """topaz/utils/image.py:64-85"""
+def downsample_file(path, scale, output, verbose=False, float16=False):
+    """topaz/utils/image.py:64-85.  float16: the MRC output is stored as float16 (mode 12), encoded on the device (tpz_encode)."""
     import sys
+    if float16 and os.path.splitext(output or '')[1] != '.mrc':
+        raise ValueError('--float16 stores MRC mode 12: the output must be an .mrc file, not ' + str(output))
     image = load_image(path, make_image=False)
     image, header, extended_header = image if type(image) is tuple else (image, None, None)
     image = image.astype(np.float32)
-    small = downsample(image, scale)
+    stored = None
+    if float16:
+        import torch
+        from .. import runtime as rt
+        from ..streaming import warn_overflow
+        if image.ndim != 2:
+            raise NotImplementedError('downsample: 2-D arrays only')
+        y = downsample_device(torch.from_numpy(np.ascontiguousarray(image)), scale)
+        half, lost = rt.encode(y, rt.ENC_F16)
+        small, stored = y.cpu().numpy(), half.cpu().numpy()
+        if lost:
+            warn_overflow(output, lost)
+    else:
+        small = downsample(image, scale)
     if header:
         header = header._replace(ny=small.shape[0], nx=small.shape[1])
     if verbose:
         print('Downsample image:', path, file=sys.stderr)
         print('From', image.shape, 'to', small.shape, file=sys.stderr)
-    save_image(small, output, header=header, extended_header=extended_header)
+    save_image(small if stored is None else stored, output, header=header, extended_header=extended_header)
     return small

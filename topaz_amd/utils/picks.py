@@ -58,6 +58,7 @@ class Plan(NamedTuple):
     micrographs: List[Micrograph]
     header: bytes               # the 1024-byte MRC header of the stack
     star: str                   # the STAR file's text
+    float16: bool = False       # the stack stores float16 (MRC mode 12) instead of float32
 
 
 class Record(NamedTuple):
@@ -82,13 +83,25 @@ def check_boxes(name: str, xy: np.ndarray, size: int) -> None:
                          'low edge of the micrograph')
 
 
+def particle_bytes(mz: int, resize: int, float16: bool = False) -> int:
+    """bytes of one particle in the stack: mz frames of resize^2 pixels, 4 bytes each, or 2 under --float16"""
+    return (2 if float16 else 4) * mz * resize * resize
+
+
+def particle_byte_offset(index: int, out_bytes: int) -> int:
+    """byte of particle `index` in the stack file: behind the 1024-byte header (the stack has no extended header)"""
+    return 1024 + out_bytes * int(index)
+
+
 def plan_from_records(records: Sequence[Record], output_file: str, size: int, resize: int, mz: int, cella, cellb,
-                      metadata_file: Optional[str]):
+                      metadata_file: Optional[str], float16: bool = False):
     """(stack header bytes, STAR path, STAR text) of the particles in `records`, in that order -- the half of the planner that
     does not care where the picks came from: `particle_stack` reads them from a table, `extract --particle-stack` has them in
-    memory.  resize: the written box size (== size when off); cella / cellb: of the first micrograph's header."""
+    memory.  resize: the written box size (== size when off); cella / cellb: of the first micrograph's header; float16: the
+    header says mode 12."""
     N = int(sum(len(r.xy) for r in records))
-    header = mrc.header_struct.pack(*list(mrc.make_header((N * mz, resize, resize), cella, cellb, mz=mz, dtype=np.float32)))
+    header = mrc.header_struct.pack(*list(mrc.make_header((N * mz, resize, resize), cella, cellb, mz=mz,
+                                                          dtype=np.float16 if float16 else np.float32)))
 
     stack_name = os.path.basename(output_file)
     star_path = os.path.splitext(output_file)[0] + '.star'
@@ -112,7 +125,8 @@ def plan_from_records(records: Sequence[Record], output_file: str, size: int, re
 
 
 def plan_particle_stack(input_file: str, output_file: str, threshold: float, size: Optional[int], resize: int,
-                        image_root: Optional[str], image_ext: str, metadata_file: Optional[str], log=None) -> Plan:
+                        image_root: Optional[str], image_ext: str, metadata_file: Optional[str], log=None,
+                        float16: bool = False) -> Plan:
     """everything of create_particle_stack but the pixels; raises ValueError / FileNotFoundError on bad input.
     log: where the progress lines go (default: sys.stderr as it is at the call, not at import)"""
     log = sys.stderr if log is None else log
@@ -161,8 +175,8 @@ def plan_particle_stack(input_file: str, output_file: str, threshold: float, siz
                                       (h.ny, h.nx) if z == 1 else (z, h.ny, h.nx)))
         records.append(Record(name, xy, coords['score'].values if 'score' in coords else None))
 
-    header, star_path, star = plan_from_records(records, output_file, size, resize, mz, cella, cellb, metadata_file)
-    return Plan(output_file, star_path, size, resize, mz, N, micrographs, header, star)
+    header, star_path, star = plan_from_records(records, output_file, size, resize, mz, cella, cellb, metadata_file, float16)
+    return Plan(output_file, star_path, size, resize, mz, N, micrographs, header, star, float16)
 
 
 def resize_operators(size: int, resize: int) -> np.ndarray:
@@ -196,20 +210,35 @@ class StackWriter:
     DEPTH = 2
 
     def __init__(self, ctx, path: str, size: int, resize: int, mz: int, budget_bytes: int = DEFAULT_BUDGET, capacity: int = 0,
-                 placeholder: bool = True):
+                 placeholder: bool = True, float16: bool = False):
         """capacity: particles per ring slot to start with (it grows to the largest chunk seen); placeholder: write the 1024
-        bytes the header will replace (rank 0)"""
+        bytes the header will replace (rank 0); float16: a chunk is encoded to float16 on the device on its way to the pinned
+        slot (ResultRing.put's `encode`) and a particle takes half the bytes of the file"""
+        from .. import runtime as rt
         self.ctx, self.path, self.S, self.R, self.mz = ctx, path, size, resize, mz
         self.ops = resize_operators(size, resize) if resize != size else None
-        self.out_bytes = 4 * mz * resize * resize
-        dev_bytes = self.out_bytes + (4 * mz * (size * size + 2 * size * resize) if resize != size else 0)
+        self.encode = rt.ENC_F16 if float16 else None
+        self.out_bytes = particle_bytes(mz, resize, float16)
+        # (the chunk size follows the float32 the device holds, whatever the file stores: the same chunks either way)
+        dev_bytes = 4 * mz * resize * resize + (4 * mz * (size * size + 2 * size * resize) if resize != size else 0)
         self.per_chunk = max(1, int(budget_bytes) // dev_bytes)
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT, 0o666)
         if placeholder:
             os.pwrite(self.fd, bytes(1024), 0)
-        self.ring = streaming.ResultRing(ctx, lambda chunk, at: streaming.pwrite_all(self.fd, chunk, at), self.DEPTH)
+        self.ring = streaming.ResultRing(ctx, lambda chunk, at: streaming.pwrite_all(self.fd, chunk, at), self.DEPTH,
+                                         on_overflow=self._overflowed)
         if capacity:
-            self.ring.reserve(min(self.per_chunk, capacity) * self.out_bytes)
+            self.ring.reserve(self._slot_bytes(min(self.per_chunk, capacity)))
+
+    def _slot_bytes(self, particles: int) -> int:
+        """ring slot bytes for a chunk of that many particles"""
+        from .. import runtime as rt
+        pixels = particles * self.mz * self.R * self.R
+        return 4 * pixels if self.encode is None else rt.Stage.encode_bytes(self.ctx, self.encode, pixels)
+
+    def _overflowed(self, lost: int, at: int) -> None:
+        first = (at - 1024) // self.out_bytes
+        streaming.warn_overflow(f'{self.path} (the chunk of particles from {first + 1} on)', lost)
 
     def check(self) -> None:
         self.ring.check()
@@ -219,9 +248,9 @@ class StackWriter:
         from .. import runtime as rt
         for c0 in range(0, len(xy), self.per_chunk):
             part = xy[c0:c0 + self.per_chunk]
-            self.ring.reserve(len(part) * self.out_bytes)       # (a growth drains the ring: before the launch, not after it)
+            self.ring.reserve(self._slot_bytes(len(part)))      # (a growth drains the ring: before the launch, not after it)
             out = rt.particle_stack(img, part, self.S, self.R, self.ops, ctx=self.ctx)
-            self.ring.put(out, 1024 + self.out_bytes * (first + c0))
+            self.ring.put(out, particle_byte_offset(first + c0, self.out_bytes), encode=self.encode)
 
     def close(self) -> None:
         """wait for the last write, free the ring, close the file (idempotent; a writer failure stays available to check())"""
@@ -261,7 +290,7 @@ def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAUL
     mine = parallel.shard_indices(len(plan.micrographs), rank, world)
     mics = [plan.micrographs[i] for i in mine]
     writer = StackWriter(ctx, plan.output, plan.size, plan.resize, plan.mz, budget_bytes,
-                         capacity=max([len(m.xy) for m in mics] or [0]), placeholder=(rank == 0))
+                         capacity=max([len(m.xy) for m in mics] or [0]), placeholder=(rank == 0), float16=plan.float16)
     try:
         for j, (path, img) in enumerate(streaming.ImageFeed([m.path for m in mics], ctx)):
             m = mics[j]
@@ -280,14 +309,14 @@ def write_particle_stack(plan: Plan, device: int = 0, budget_bytes: int = DEFAUL
 
 def create_particle_stack(input_file: str, output_file: str, threshold: float, size: Optional[int], resize: int,
                           image_root: Optional[str], image_ext: str, metadata_file: Optional[str], device: int = 0,
-                          budget_bytes: int = DEFAULT_BUDGET) -> Plan:
+                          budget_bytes: int = DEFAULT_BUDGET, float16: bool = False) -> Plan:
     """topaz/utils/picks.py:71-197 on the MI355X; budget_bytes: device bytes of one chunk of particles.  Under `--gpus N`
     (WORLD_SIZE > 1) every rank plans the whole table and cuts its share of the micrographs into the one output file."""
     from .. import parallel
     under_ranks = int(os.environ.get('WORLD_SIZE', '1')) > 1
     quiet = under_ranks and int(os.environ.get('RANK', '0')) != 0
     plan = plan_particle_stack(input_file, output_file, threshold, size, resize, image_root, image_ext, metadata_file,
-                               **({'log': io.StringIO()} if quiet else {}))
+                               float16=float16, **({'log': io.StringIO()} if quiet else {}))
     ranks = parallel.init_from_env() if under_ranks else (0, 0, 1)      # (after the plan: bad input fails before the rendezvous)
     if ranks[2] > 1:
         device = parallel.rank_device(ranks[1])
@@ -358,8 +387,9 @@ class ExtractStack:
     go (particle_offset); finish() gathers the kept picks to rank 0 (parallel.gather_pick_tables), which writes the STAR."""
 
     def __init__(self, output: str, size: int, resize: int, threshold: float, metadata_file: Optional[str],
-                 ranks: Tuple[int, int, int] = (0, 0, 1), budget_bytes: int = DEFAULT_BUDGET):
+                 ranks: Tuple[int, int, int] = (0, 0, 1), budget_bytes: int = DEFAULT_BUDGET, float16: bool = False):
         self.output, self.size, self.threshold, self.metadata_file = output, int(size), float(threshold), metadata_file
+        self.float16 = bool(float16)
         self.resize = self.size if resize < 0 else int(resize)
         self.rank, self.local_rank, self.world = ranks
         self.budget_bytes = budget_bytes
@@ -403,7 +433,7 @@ class ExtractStack:
         first = self.claim(len(xy))
         if self.writer is None:
             self.writer = StackWriter(rt.get_context(image.device.index), self.output, self.size, self.resize, 1,
-                                      self.budget_bytes, placeholder=(self.rank == 0))
+                                      self.budget_bytes, placeholder=(self.rank == 0), float16=self.float16)
         self.writer.cut(image, xy, first)
         self.rows.append((index, s32[keep], xy))
         return len(xy)
@@ -441,8 +471,8 @@ class ExtractStack:
             records = [Record(os.path.basename(paths[i]), tables[i][1], scores_as_read_back(tables[i][1], tables[i][0]))
                        for i in sorted(tables) if len(tables[i][0])]
             header, star_path, star = plan_from_records(records, self.output, self.size, self.resize, 1, self.cell[0],
-                                                        self.cell[1], self.metadata_file)
-            seal_particle_stack(self.output, header, n, 4 * self.resize * self.resize, star_path, star)
+                                                        self.cell[1], self.metadata_file, self.float16)
+            seal_particle_stack(self.output, header, n, particle_bytes(1, self.resize, self.float16), star_path, star)
         return n
 
 
