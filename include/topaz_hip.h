@@ -384,10 +384,13 @@ int tpz_ctx_set_lanes(tpz_ctx* ctx, int on);
  * Every image of a batch has a workspace of its own and two batches are in flight: the batch is cut to what fits 90 % of the
  * free device memory (tpz_ctx_set_batch_memory(ctx, bytes): that many bytes instead; 0 = automatic), below 2 the pass falls
  * back to single patches on the lanes -- a large tile costs launches, not an out-of-memory error.
- * tpz_prof_launches: kernel launches the library has issued on this context (convolutions, elementwise, NMS sweeps excluded). */
+ * tpz_prof_launches: kernel launches the library has issued on this context (convolutions, elementwise, NMS sweeps excluded).
+ * tpz_ctx_pool_stats: the workspace buffers all pools of the context cache (the ctx pool, the patch lanes', those of the batched
+ * passes), their bytes, and how many are marked in use -- 0 between calls; any out pointer may be NULL. */
 int tpz_ctx_set_batch(tpz_ctx* ctx, int n);
 int tpz_ctx_set_batch_memory(tpz_ctx* ctx, long long bytes);
 long long tpz_prof_launches(tpz_ctx* ctx);
+int tpz_ctx_pool_stats(tpz_ctx* ctx, long long* buffers, long long* bytes, long long* buffers_in_use);
 /* Patch windows: a patch of tpz_denoise_2d keeps only its centre (topaz/denoise.py:299-323: patch_size pixels of a
  * patch_size + 2*padding tile), so each layer computes only the rectangle of its tensor that those pixels depend on (the
  * U-Net's receptive field is ~230 pixels, the CLI's default padding 500).  The statistics of the normalisation are still the

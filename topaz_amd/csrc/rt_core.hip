@@ -90,9 +90,9 @@ int fail(tpz_ctx* ctx, const char* fmt, ...) {
     return 1;
 }
 
-void* pool_alloc(tpz_ctx* ctx, size_t bytes) {
+// a buffer of at least `bytes` from `pool`, marked used: the smallest cached one that fits, else a new one
+static void* pool_alloc(tpz_ctx* ctx, std::vector<tpz_ctx::Buf>& pool, size_t bytes) {
     if (bytes == 0) bytes = 16;
-    std::vector<tpz_ctx::Buf>& pool = *ctx->pool_cur;
     int best = -1;
     for (int i = 0; i < (int)pool.size(); ++i) {
         auto& b = pool[i];
@@ -140,9 +140,13 @@ void* pool_alloc(tpz_ctx* ctx, size_t bytes) {
     pool.push_back({p, rounded, true});
     return p;
 }
-void pool_release(tpz_ctx* ctx, void* p) {
-    for (auto& b : *ctx->pool_cur)
-        if (b.p == p) { b.used = false; return; }
+WorkBuf::WorkBuf(tpz_ctx* ctx, size_t bytes) : pool_(ctx->pool_cur), p_(pool_alloc(ctx, *ctx->pool_cur, bytes)) {}
+// (by device pointer, not by index: a trim of the pool erases entries)
+void WorkBuf::release() {
+    if (p_)
+        for (auto& b : *pool_)
+            if (b.p == p_) { b.used = false; break; }
+    p_ = nullptr;
 }
 
 // ---- the overflow flag of a 2xf16 pass: cleared on the ctx stream before the pass, read back once the stream has drained
@@ -478,6 +482,21 @@ int tpz_ctx_set_batch_memory(tpz_ctx* ctx, long long bytes) {
     return 0;
 }
 long long tpz_prof_launches(tpz_ctx* ctx) { return ctx ? ctx->n_launches : 0; }
+int tpz_ctx_pool_stats(tpz_ctx* ctx, long long* buffers, long long* bytes, long long* buffers_in_use) {
+    if (!ctx) return fail(nullptr, "ctx is NULL");
+    long long n = 0, b = 0, u = 0;
+    auto add = [&](const std::vector<tpz_ctx::Buf>& pl) {
+        for (const auto& e : pl) { ++n; b += (long long)e.bytes; u += e.used ? 1 : 0; }
+    };
+    add(ctx->pool);
+    for (const auto& ln : ctx->lanes) add(ln.pool);
+    for (const auto& lane_pools : ctx->rec_pools)
+        for (const auto& pl : lane_pools) add(pl);
+    if (buffers) *buffers = n;
+    if (bytes) *bytes = b;
+    if (buffers_in_use) *buffers_in_use = u;
+    return 0;
+}
 
 int tpz_ctx_set_persist(tpz_ctx* ctx, int mode, int workgroups) {
     if (!ctx || mode < 0 || mode > 2 || workgroups < 0) return fail(ctx, "tpz_ctx_set_persist: bad arguments");

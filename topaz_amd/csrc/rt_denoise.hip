@@ -57,15 +57,14 @@ int denoise_region(tpz_model* m, const Slot& view, float* d_out_dense, int mode 
     HIPCHK(ctx, e);
     // (x - mu)/std once, into a dense buffer every reader of slot 0 (first conv, dec1 concat) DMA-loads
     const size_t n = (size_t)view.D * view.H * view.W;
-    float* xn = (float*)pool_alloc(ctx, n * sizeof(float));
-    if (!xn) return fail(ctx, "out of device memory");
+    const WorkBuf xnb(ctx, n * sizeof(float));
+    if (!xnb) return fail(ctx, "out of device memory");
+    float* xn = xnb.as<float>();
     e = enqueue(ctx, [=](hipStream_t st) { return launch_affine_dev(vp_, vD, vH, vW, vps, vpitch, nrm, xn, st); });
-    if (e != hipSuccess) { pool_release(ctx, xn); return fail(ctx, "affine_dev failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ctx, "affine_dev failed: %s", hipGetErrorString(e));
     std::vector<Slot> slots(m->n_slots);
     set_dense(slots[0], xn, 1, view.D, view.H, view.W);
-    const int rc = run_program(m, slots, d_out_dense, nrm, split, keep);
-    pool_release(ctx, xn);
-    return rc;
+    return run_program(m, slots, d_out_dense, nrm, split, keep);
 }
 
 int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int patch, int pad, float* d_out, bool split) {
@@ -106,7 +105,8 @@ int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int patch, in
             v.pitch = W;
             v.ps = (long long)H * W;
             v.cs = v.ps;
-            float* tmp = (float*)pool_alloc(ctx, (size_t)ph * pw * sizeof(float));
+            const WorkBuf tmpb(ctx, (size_t)ph * pw * sizeof(float));      // (this patch's)
+            float* tmp = tmpb.as<float>();
             if (!tmp) { rc_all = fail(ctx, "out of device memory"); break; }
             const int oi = i - si, oj = j - sj;
             const int ch = std::min(patch, std::min(H - i, ph - oi)), cw = std::min(patch, std::min(W - j, pw - oj));
@@ -119,7 +119,6 @@ int denoise_2d_pass(tpz_model* m, const float* d_in, int H, int W, int patch, in
                 hipError_t e = enqueue(ctx, [=](hipStream_t st) { return launch_copy_box(src_, 0, pw, dst_, 0, W, 1, ch, cw, st); });
                 if (e != hipSuccess) rc = fail(ctx, "copy_box failed: %s", hipGetErrorString(e));
             }
-            pool_release(ctx, tmp);
             if (rc) rc_all = rc;
         }
     const std::string err = ctx->err;
@@ -153,7 +152,7 @@ int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int pa
     const int lanes_used = ctx->lanes_on ? ctx->lanes_live : 1;
     const int per_lane = batched ? batch : 1;
     const int n_inst = lanes_used * per_lane;
-    float *tiles[N_LANES * SPLIT_MULTI_MAX] = {}, *touts[N_LANES * SPLIT_MULTI_MAX] = {};
+    WorkBuf tiles[N_LANES * SPLIT_MULTI_MAX], touts[N_LANES * SPLIT_MULTI_MAX];      // each from its instance's pool
     int rc = 0;
     auto inst_enter = [&](int inst) {
         if (batched) {
@@ -163,8 +162,8 @@ int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int pa
     };
     for (int l = 0; l < n_inst; ++l) {
         inst_enter(l);
-        tiles[l] = (float*)pool_alloc(ctx, tn * sizeof(float));
-        touts[l] = (float*)pool_alloc(ctx, tn * sizeof(float));
+        tiles[l] = WorkBuf(ctx, tn * sizeof(float));
+        touts[l] = WorkBuf(ctx, tn * sizeof(float));
         if (!tiles[l] || !touts[l]) rc = fail(ctx, "out of device memory");
     }
     int n_tile = 0, tile_index = 0, slot = 0, slots_left = 0, n_batches = 0;
@@ -184,7 +183,7 @@ int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int pa
                     --slots_left;
                 }
                 inst_enter(l);
-                float *tile = tiles[l], *tout = touts[l];
+                float *tile = tiles[l].as<float>(), *tout = touts[l].as<float>();
                 hipError_t e = enqueue(ctx, [=](hipStream_t st) {
                     return launch_extract_tile3d(d_in, D, H, W, i - pad, j - pad, k - pad, d, g, tile, st);
                 });
@@ -209,11 +208,6 @@ int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int pa
             }
     const std::string err = ctx->err;
     if (batched && ctx->rec_on && !rc && rec_flush(ctx)) rc = 1;
-    for (int l = 0; l < n_inst; ++l) {
-        inst_enter(l);
-        if (tiles[l]) pool_release(ctx, tiles[l]);
-        if (touts[l]) pool_release(ctx, touts[l]);
-    }
     if (batched) rec_abort(ctx);
     if (lanes_end(ctx) && !rc) rc = 1;
     if (rc && !err.empty()) ctx->err = err;

@@ -385,15 +385,16 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
     if (sp.sub_with_skip) {
         // one plain sub-pixel launch: low-resolution source + the space-to-depth copy of the 1-channel skip source
         if (s2.pitch != s2.W || s2.ps != (long long)s2.H * s2.W) return fail(ctx, "2xf16 decoder needs a dense skip source");
-        float* X = (float*)pool_alloc(ctx, (size_t)8 * s1.H * s1.W * sizeof(float));
-        if (!X) return fail(ctx, "out of device memory");
+        const WorkBuf Xb(ctx, (size_t)8 * s1.H * s1.W * sizeof(float));
+        if (!Xb) return fail(ctx, "out of device memory");
+        float* X = Xb.as<float>();
         hipError_t e;
         {
             const float* sp_ = s2.p; unsigned* fl_ = ctx->d_flag;
             const int h1 = s1.H, w1 = s1.W, h2 = s2.H, w2 = s2.W;
             e = enqueue(ctx, [=](hipStream_t st) { return launch_s2d_split(sp_, X, 1, h1, w1, h2, w2, 2, fl_, st); });
         }
-        if (e != hipSuccess) { pool_release(ctx, X); return fail(ctx, "s2d failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(ctx, "s2d failed: %s", hipGetErrorString(e));
         SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.cout, dhw(s1), 2, dhw(dst), 0, 1, L.slope);
         a.in2 = reinterpret_cast<const uint4*>(X);
         a.cells_in = a.cells_in1 + 1;
@@ -404,23 +405,23 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.out = reinterpret_cast<uint4*>(dst.p);
         a.n_chunks = sp.n_chunks_low;
         const double fl = 2.0 * L.cout * (ph.c1 * 9.0 * 4.0 + 25.0 * 4.0) * (double)s1.H * s1.W;
-        const int rc = launch_split(ctx, *sp.ks_sub, a, sp.n_cog_sub, fl, launch_window(dst.need, lattice(a), 2));
-        pool_release(ctx, X);
-        return rc;
+        return launch_split(ctx, *sp.ks_sub, a, sp.n_cog_sub, fl, launch_window(dst.need, lattice(a), 2));
     }
     // ---- skip-source part over the full grid: bias, no activation
+    WorkBuf Xb;
     float* Xs2d = nullptr;
     if (sp.low_with_skip) {
         if (s2.pitch != s2.W || s2.ps != (long long)s2.H * s2.W) return fail(ctx, "2xf16 decoder needs a dense skip source");
-        Xs2d = (float*)pool_alloc(ctx, (size_t)8 * s1.D * s1.H * s1.W * sizeof(float));
-        if (!Xs2d) return fail(ctx, "out of device memory");
+        Xb = WorkBuf(ctx, (size_t)8 * s1.D * s1.H * s1.W * sizeof(float));
+        if (!Xb) return fail(ctx, "out of device memory");
+        Xs2d = Xb.as<float>();
         hipError_t e;
         {
             const float* sp_ = s2.p; unsigned* fl_ = ctx->d_flag;
             const int d1 = s1.D, h1 = s1.H, w1 = s1.W, h2 = s2.H, w2 = s2.W, dims = L.dims;
             e = enqueue(ctx, [=](hipStream_t st) { return launch_s2d_split(sp_, Xs2d, d1, h1, w1, h2, w2, dims, fl_, st); });
         }
-        if (e != hipSuccess) { pool_release(ctx, Xs2d); return fail(ctx, "s2d failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(ctx, "s2d failed: %s", hipGetErrorString(e));
     } else if (sp.ki_skip_stem) {
         ConvArgs a;
         memset(&a, 0, sizeof a);
@@ -485,9 +486,7 @@ int run_conv_split_phases(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, const
         a.n_chunks = sp.n_chunks_low;
         const double fl = conv_flops(L.cout, ph.c1, ph.k1, L.dims, dhw(s1)) * (1 << L.dims);
         const SplitKernelInfo& kk = sp.ks_sub ? *sp.ks_sub : (sp.low_with_skip ? *sp.ks_low_plain : *sp.ks_low);
-        const int rc = launch_split(ctx, kk, a, sp.ks_sub ? sp.n_cog_sub : sp.n_cog_low, fl, launch_window(dst.need, lattice(a), 2));
-        if (Xs2d) pool_release(ctx, Xs2d);
-        if (rc) return 1;
+        if (launch_split(ctx, kk, a, sp.ks_sub ? sp.n_cog_sub : sp.n_cog_low, fl, launch_window(dst.need, lattice(a), 2))) return 1;
     }
     return 0;
 }
@@ -501,8 +500,9 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
     const size_t rows = (size_t)s1.D * s1.H;
     // conv output geometry (dst is the pooled tensor when the max-pool is fused)
     const int Hc = layer_out_dhw(L, dhw(s1)).H, Wc = layer_out_dhw(L, dhw(s1)).W;      // (dilation 1: prepare_split)
-    float* X = (float*)pool_alloc(ctx, (size_t)ncell * 8 * rows * Wc * sizeof(float));
-    if (!X) return fail(ctx, "out of device memory");
+    const WorkBuf Xb(ctx, (size_t)ncell * 8 * rows * Wc * sizeof(float));
+    if (!Xb) return fail(ctx, "out of device memory");
+    float* X = Xb.as<float>();
     // the window of the conv (dst.need: in the coordinates of the conv output, also when the max-pool is fused)
     const Window w = launch_window(dst.need, {dst.D, Hc, Wc});
     // (2-D with a window: only the rows and columns the windowed conv reads -- output row y reads input rows y - pad .. y + pad)
@@ -518,7 +518,7 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
             e = enqueue(ctx, [=](hipStream_t st) { return launch_shiftx_split(sp_, X, k, pad, rows, W1, Wc, fl_, st); });
         }
     }
-    if (e != hipSuccess) { pool_release(ctx, X); return fail(ctx, "shiftx failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ctx, "shiftx failed: %s", hipGetErrorString(e));
     SplitArgs a = split_args(ctx, X, ncell, {s1.D, s1.H, Wc}, L.cout, {dst.D, Hc, Wc}, 1, dhw(dst), L.dims == 3 ? L.k : 0, L.pad,
                              L.slope);
     a.pad_x = 0;                       // (the kx taps are channels of X)
@@ -527,9 +527,7 @@ int run_stem_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, b
     a.bias = bias_view(ctx, rt.d_bias);
     a.out = reinterpret_cast<uint4*>(dst.p);
     a.n_chunks = rt.s_n_chunks;
-    const int rc = launch_split(ctx, ks, a, rt.s_n_cog, conv_flops(L.cout, 1, L.k, L.dims, {dst.D, Hc, Wc}), w);
-    pool_release(ctx, X);
-    return rc;
+    return launch_split(ctx, ks, a, rt.s_n_cog, conv_flops(L.cout, 1, L.k, L.dims, {dst.D, Hc, Wc}), w);
 }
 
 // 1-output-channel last conv on the 2xf16 path: k virtual output channels (one per kx tap) over W + 2*pad columns
@@ -563,8 +561,9 @@ int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, c
     const SplitKernelInfo& ks = *rt.ks_last;
     const int Wp = dst.W + 2 * L.pad;
     const size_t rows = (size_t)dst.D * dst.H;
-    float* Y = (float*)pool_alloc(ctx, (size_t)L.k * rows * Wp * sizeof(float));
-    if (!Y) return fail(ctx, "out of device memory");
+    const WorkBuf Yb(ctx, (size_t)L.k * rows * Wp * sizeof(float));
+    if (!Yb) return fail(ctx, "out of device memory");
+    float* Y = Yb.as<float>();
     const Dhw lat = {dst.D, dst.H, Wp};
     SplitArgs a = split_args(ctx, s1.p, (int)split_cells(s1.C), dhw(s1), L.k, lat, 1, lat, L.dims == 3 ? L.k : 0, L.pad, 1.f);
     a.cells_out = 1;
@@ -591,18 +590,24 @@ int run_last_split(tpz_ctx* ctx, const LayerRT& rt, const Slot& s1, Slot& dst, c
                                });
         if (e != hipSuccess) rc = fail(ctx, "shiftsum failed: %s", hipGetErrorString(e));
     }
-    pool_release(ctx, Y);
     return rc;
 }
 
+// the buffers of the workspace pool behind a slot (a Slot is a view and is copied freely): run_program holds one per slot
+struct SlotBufs {
+    WorkBuf own;      // the tensor the producing layer wrote (none: the caller's input or output)
+    WorkBuf alt;      // the same tensor converted to the other format for a consumer that needs it
+};
+
 // the slot's 2-D tensor in the wanted format: the producer's own buffer, or a converted copy made once
-float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
+float* slot_as(tpz_ctx* ctx, const Slot& s, SlotBufs& b, bool want_split) {
     if (s.split == want_split) return s.p;
-    if (s.alt) return s.alt;
+    if (b.alt) return b.alt.as<float>();
     if (s.pitch != s.W || s.ps != (long long)s.H * s.W || s.cs != s.ps * s.D) return nullptr;
     const size_t c_alloc = want_split ? split_cells(s.C) * 8 : (size_t)s.C;
-    float* q = (float*)pool_alloc(ctx, c_alloc * s.D * s.H * s.W * sizeof(float));
-    if (!q) return nullptr;
+    WorkBuf qb(ctx, c_alloc * s.D * s.H * s.W * sizeof(float));
+    if (!qb) return nullptr;
+    float* q = qb.as<float>();
     // cells are [c/8][D*H*W]: a volume converts as an image of D*H rows
     hipError_t e;
     {
@@ -612,31 +617,32 @@ float* slot_as(tpz_ctx* ctx, Slot& s, bool want_split) {
             return want_split ? launch_to_split(sp_, q, C, R, W, fl_, st) : launch_from_split(sp_, q, C, R, W, st);
         });
     }
-    if (e != hipSuccess) { pool_release(ctx, q); return nullptr; }
-    s.alt = q;
+    if (e != hipSuccess) return nullptr;
+    b.alt = std::move(qb);
     return q;
 }
 // ... the slot as a source in that format; .p == nullptr: the conversion failed
-Slot source_view(tpz_ctx* ctx, Slot& s, bool want_split) {
+Slot source_view(tpz_ctx* ctx, const Slot& s, SlotBufs& b, bool want_split) {
     Slot v = s;
-    v.p = slot_as(ctx, s, want_split);
+    v.p = slot_as(ctx, s, b, want_split);
     v.split = want_split;
     return v;
 }
 
 // Gives layer i its destination: C channels of `o` voxels as fp32 planes or (split) as split cells, which take the bytes of fp32
-// with the channels rounded up to whole 8-channel cells -- d_out for the last layer, else a buffer of the workspace pool that the
-// slot owns.  `need`: the part of the tensor anything reads.
-int make_dst(tpz_ctx* ctx, Slot& dst, int i, bool last, float* d_out, int C, bool split, const Dhw& o, const Rect& need) {
+// with the channels rounded up to whole 8-channel cells -- d_out for the last layer, else a buffer of the workspace pool that
+// `b` then owns (whatever it held before goes back).  `need`: the part of the tensor anything reads.
+int make_dst(tpz_ctx* ctx, Slot& dst, SlotBufs& b, int i, bool last, float* d_out, int C, bool split, const Dhw& o, const Rect& need) {
     const size_t c_alloc = split ? split_cells(C) * 8 : (size_t)C;
-    float* p = last ? d_out : (float*)pool_alloc(ctx, c_alloc * o.D * o.H * o.W * sizeof(float));
+    WorkBuf nb = last ? WorkBuf() : WorkBuf(ctx, c_alloc * o.D * o.H * o.W * sizeof(float));
+    float* p = last ? d_out : nb.as<float>();
     if (!p) return fail(ctx, "out of device memory (layer %d)", i);
     set_dense(dst, p, C, o.D, o.H, o.W);
     dst.need = need;
     dst.split = split;
     dst.pooled = false;
-    dst.alt = nullptr;
-    dst.owned = !last;
+    b.own = std::move(nb);
+    b.alt.release();
     return 0;
 }
 
@@ -858,6 +864,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
     std::vector<Rect> need;
     if (keep && slots[0].set) need = need_regions(m, slots[0].D, slots[0].H, slots[0].W, *keep, split);
     auto need_of = [&](int slot) { return need.empty() ? Rect() : need[slot]; };
+    std::vector<SlotBufs> bufs(slots.size());      // what the slots own: back in the pool when this returns, if not before
     int rc = 0;
     for (int i = 0; i < nl && rc == 0; ++i) {
         const LayerRT& rt = m->layers[i];
@@ -891,13 +898,13 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             // a fused max-pool: the slot receives the pooled tensor (and keeps its need in the coordinates of the conv output)
             const Dhw od = {o.D, pl.fuse_pool ? o.H / 2 : o.H, pl.fuse_pool ? o.W / 2 : o.W};
             if (pl.fuse_pool && (od.H < 1 || od.W < 1)) { rc = fail(ctx, "layer %d: input too small to pool", i + 1); break; }
-            if ((rc = make_dst(ctx, dst, i, last, d_out, Co, pl.split_dst, od, need_of(L.dst)))) break;
+            if ((rc = make_dst(ctx, dst, bufs[L.dst], i, last, d_out, Co, pl.split_dst, od, need_of(L.dst)))) break;
             dst.pooled = pl.fuse_pool;
             if (pl.split_dst && last) { rc = fail(ctx, "layer %d: the result must leave as fp32", i); break; }
             // sources in the format the chosen kernels read (converted once if the producer wrote the other one)
-            const Slot v1 = source_view(ctx, slots[L.src], pl.split1);
-            const Slot v2 = s2 ? source_view(ctx, slots[L.src2], pl.split2) : Slot();
-            const Slot vres = sres ? source_view(ctx, slots[L.res], pl.split_res) : Slot();
+            const Slot v1 = source_view(ctx, slots[L.src], bufs[L.src], pl.split1);
+            const Slot v2 = s2 ? source_view(ctx, slots[L.src2], bufs[L.src2], pl.split2) : Slot();
+            const Slot vres = sres ? source_view(ctx, slots[L.res], bufs[L.res], pl.split_res) : Slot();
             if (!v1.p || (s2 && !v2.p) || (sres && !vres.p)) { rc = fail(ctx, "layer %d: tensor format conversion failed", i); break; }
             // slot 0 arrives already normalised (denoise_region); only the last layer un-normalises
             const int norm_out = (d_nrm && last) ? 1 : 0;
@@ -906,7 +913,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             case FORM_LAST: rc = run_last_split(ctx, rt, v1, dst, d_nrm, norm_out, sres ? &vres : nullptr); break;
             case FORM_PARITY: rc = run_conv_split_phases(ctx, rt, v1, v2, dst); break;
             case FORM_SPLIT_FOLD: {
-                const Slot vf = source_view(ctx, slots[rt.fold_src], true);
+                const Slot vf = source_view(ctx, slots[rt.fold_src], bufs[rt.fold_src], true);
                 if (!vf.p) rc = fail(ctx, "layer %d: tensor format conversion failed", i);
                 else rc = run_conv_split(ctx, rt, v1, nullptr, dst, nullptr, false, &vf);
                 break;
@@ -919,7 +926,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             // pooled in-plane by the producing conv: the z pairs remain
             const Slot src = s1;
             if (src.D / 2 < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
-            if ((rc = make_dst(ctx, dst, i, last, d_out, src.C, true, {src.D / 2, src.H, src.W}, need_of(L.dst)))) break;
+            if ((rc = make_dst(ctx, dst, bufs[L.dst], i, last, d_out, src.C, true, {src.D / 2, src.H, src.W}, need_of(L.dst)))) break;
             hipError_t e;
             {
                 const float* sp_ = src.p; float* dp_ = dst.p;
@@ -932,17 +939,16 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
             dst = s1;
             dst.need = need_of(L.dst);
             dst.pooled = false;
-            slots[L.src].owned = false;
-            slots[L.src].alt = nullptr;
+            bufs[L.dst] = std::move(bufs[L.src]);
         } else if (L.op == TPZ_OP_MAXPOOL2 || L.op == TPZ_OP_MAXPOOL || L.op == TPZ_OP_AVGPOOL) {
             if (s1.pitch != s1.W || s1.ps != (long long)s1.H * s1.W) { rc = fail(ctx, "maxpool needs a dense input"); break; }
             const Dhw o = layer_out_dhw(L, dhw(s1));
             if (o.D < 1 || o.H < 1 || o.W < 1) { rc = fail(ctx, "layer %d: input too small to pool", i); break; }
             const bool sp = s1.split && !last;                // pooled in the format the source has
             const float* src_p = s1.p;
-            if (s1.split && !sp) { src_p = slot_as(ctx, slots[L.src], false); if (!src_p) { rc = fail(ctx, "conversion failed"); break; } }
+            if (s1.split && !sp) { src_p = slot_as(ctx, slots[L.src], bufs[L.src], false); if (!src_p) { rc = fail(ctx, "conversion failed"); break; } }
             const int Cs = s1.C, Ds = s1.D, Hs = s1.H, Ws = s1.W;
-            if ((rc = make_dst(ctx, dst, i, last, d_out, Cs, sp, o, need_of(L.dst)))) break;
+            if ((rc = make_dst(ctx, dst, bufs[L.dst], i, last, d_out, Cs, sp, o, need_of(L.dst)))) break;
             float* dp_ = dst.p;
             const int k = L.k, dil = L.dil, dims = L.dims, pad = L.pad;
             const bool by2 = L.op == TPZ_OP_MAXPOOL2, padded = is_padded_pool(L), mean = L.op == TPZ_OP_AVGPOOL;
@@ -957,14 +963,7 @@ int run_program(tpz_model* m, std::vector<Slot>& slots, float* d_out, const floa
         }
         // release intermediates whose last reader was this layer
         for (int s = 0; s < m->n_slots; ++s)
-            if (slots[s].set && m->last_use[s] == i) {
-                if (slots[s].owned) { pool_release(ctx, slots[s].p); slots[s].owned = false; }
-                if (slots[s].alt) { pool_release(ctx, slots[s].alt); slots[s].alt = nullptr; }
-            }
-    }
-    for (auto& s : slots) {
-        if (s.owned) { pool_release(ctx, s.p); s.owned = false; }
-        if (s.alt) { pool_release(ctx, s.alt); s.alt = nullptr; }
+            if (slots[s].set && m->last_use[s] == i) { bufs[s].own.release(); bufs[s].alt.release(); }
     }
     return rc;
 }

@@ -58,8 +58,8 @@ int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, i
             const int y0 = std::max(0, ty - halo), y1 = std::min(H, ty + T + halo);
             const int x0 = std::max(0, tx - halo), x1 = std::min(W, tx + T + halo);
             const int wh = y1 - y0, ww = x1 - x0, th = std::min(T, H - ty), tw = std::min(T, W - tx);
-            float* xt = (float*)pool_alloc(ctx, (size_t)wh * ww * sizeof(float));
-            float* ot = (float*)pool_alloc(ctx, (size_t)Co * wh * ww * sizeof(float));
+            const WorkBuf xtb(ctx, (size_t)wh * ww * sizeof(float)), otb(ctx, (size_t)Co * wh * ww * sizeof(float));   // (this tile's)
+            float *xt = xtb.as<float>(), *ot = otb.as<float>();
             int rc = (!xt || !ot) ? fail(ctx, "out of device memory") : 0;
             if (!rc) {
                 const float* src = x + (size_t)y0 * W + x0;
@@ -79,8 +79,6 @@ int run_image(tpz_model* m, float* x, int D, int H, int W, float* out, int Co, i
                 });
                 if (e != hipSuccess) rc = fail(ctx, "copy_box failed: %s", hipGetErrorString(e));
             }
-            if (xt) pool_release(ctx, xt);
-            if (ot) pool_release(ctx, ot);
             if (rc) return rc;
         }
     return 0;
@@ -113,17 +111,19 @@ int forward_image(tpz_model* m, float* x, int D, int H, int W, float* out_b, int
         // a normalised image), so outliers cannot starve the rest of precision (kernels_misc.hip launch_range_fit).
         const bool scaled = ctx->range_scaling && m->layers.back().L.op == TPZ_OP_CONV && m->layers.back().L.head &&
                             m->d_bias_scaled != nullptr;
-        float *xs = nullptr, *rng = nullptr;
+        WorkBuf xsb;
+        float* rng = nullptr;
         if (scaled) {
             const size_t n_in = (size_t)D * H * W;
             rng = next_nrm(ctx);
-            xs = (float*)pool_alloc(ctx, n_in * sizeof(float));
-            if (!xs) return fail(ctx, "out of device memory");
+            xsb = WorkBuf(ctx, n_in * sizeof(float));
+            if (!xsb) return fail(ctx, "out of device memory");
+            float* xs = xsb.as<float>();
             hipError_t e = enqueue(ctx, [=](hipStream_t st) {
                 return launch_range_fit(x_b, n_in, ctx->d_absmax, rng, m->d_bias_arena, m->d_bias_scaled, m->n_bias_arena, st);
             });
             if (e == hipSuccess) e = enqueue(ctx, [=](hipStream_t st) { return launch_affine_dev(x_b, D, H, W, (long long)H * W, W, rng, xs, st); });
-            if (e != hipSuccess) { pool_release(ctx, xs); return fail(ctx, "range scaling failed: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(ctx, "range scaling failed: %s", hipGetErrorString(e));
             x_b = xs;
             ctx->bias_shift = m->d_bias_scaled - m->d_bias_arena;
             ctx->scaled_pass = true;
@@ -131,7 +131,7 @@ int forward_image(tpz_model* m, float* x, int D, int H, int W, float* out_b, int
         const int rc = run_image(m, x_b, D, H, W, out_b, Co, Do, Ho, Wo, true);
         ctx->bias_shift = 0;
         ctx->scaled_pass = false;
-        if (xs) pool_release(ctx, xs);
+        xsb.release();                     // (before an fp32 re-run takes its workspace)
         if (rc) return 1;
         if (scaled) {
             const size_t n_out = (size_t)Co * Do * Ho * Wo;
@@ -190,16 +190,14 @@ int tpz_model_calibrate(tpz_model* m, const float* d_in, int D, int H, int W, fl
     tpz_model_out_channels(m, &Co);
     const size_t n_out = (size_t)Co * Do * Ho * Wo;
     float* x = const_cast<float*>(d_in);
-    float* y_split = (float*)pool_alloc(ctx, n_out * sizeof(float));
-    float* y_exact = (float*)pool_alloc(ctx, n_out * sizeof(float));
+    const WorkBuf ysb(ctx, n_out * sizeof(float)), yeb(ctx, n_out * sizeof(float));
+    float *y_split = ysb.as<float>(), *y_exact = yeb.as<float>();
     int rc = (!y_split || !y_exact) ? fail(ctx, "out of device memory") : 0;
     unsigned overflow = 0;
     if (!rc) rc = forward_image(m, x, D, H, W, y_split, Co, Do, Ho, Wo, PASS_SPLIT, &overflow);
     if (!rc && overflow) out->overflow = 1;                  // the runtime re-runs such an image in fp32 anyway
     if (!rc && !overflow) rc = forward_image(m, x, D, H, W, y_exact, Co, Do, Ho, Wo, PASS_FP32);
     if (!rc && !overflow) rc = delta_stats(ctx, y_split, y_exact, n_out, &out->d);
-    if (y_split) pool_release(ctx, y_split);
-    if (y_exact) pool_release(ctx, y_exact);
     if (rc || overflow) return rc;
     out->rms_delta = std::sqrt(out->d.sum_sq / (double)n_out);
     if (bar > 0.f && !(out->d.max_abs_delta <= bar)) {      // (an infinite figure trips as well)
@@ -255,15 +253,16 @@ int tpz_conv_split_2d(tpz_ctx* ctx, const float* d_in, int cin, int H, int W, co
     if (!rc && h_post_shift) rc = upload_chan(ctx, &tmp, h_post_shift, cout, &rt.d_post_shift);
     if (!rc && h_head_w) { rc = upload_chan(ctx, &tmp, h_head_w, cout, &rt.d_head_w); rt.head_b = head_b; }
     Slot s1, sres, dst;
-    float *x_s = nullptr, *r_s = nullptr, *y_s = nullptr;
+    WorkBuf xb, yb, rb;
     const int Hr = Ho + 2 * res_crop, Wr = Wo + 2 * res_crop;
     if (!rc) {
-        x_s = (float*)pool_alloc(ctx, split_cells(cin) * 8 * (size_t)H * W * 4);
-        y_s = (float*)pool_alloc(ctx, split_cells(cout) * 8 * (size_t)Ho * Wo * 4);
-        if (d_res) r_s = (float*)pool_alloc(ctx, split_cells(cout) * 8 * (size_t)Hr * Wr * 4);
-        if (!x_s || !y_s || (d_res && !r_s)) rc = fail(ctx, "out of device memory");
+        xb = WorkBuf(ctx, split_cells(cin) * 8 * (size_t)H * W * 4);
+        yb = WorkBuf(ctx, split_cells(cout) * 8 * (size_t)Ho * Wo * 4);
+        if (d_res) rb = WorkBuf(ctx, split_cells(cout) * 8 * (size_t)Hr * Wr * 4);
+        if (!xb || !yb || (d_res && !rb)) rc = fail(ctx, "out of device memory");
     }
     if (!rc) {
+        float *x_s = xb.as<float>(), *y_s = yb.as<float>(), *r_s = rb.as<float>();
         (void)flag_clear(ctx);
         (void)launch_to_split(d_in, x_s, cin, H, W, ctx->d_flag, ctx->stream);
         set_dense(s1, x_s, cin, 1, H, W); s1.split = true;
@@ -275,9 +274,6 @@ int tpz_conv_split_2d(tpz_ctx* ctx, const float* d_in, int cin, int H, int W, co
         if (flag_read(ctx, &flag, false) != hipSuccess) rc = fail(ctx, "tpz_conv_split_2d: kernel failed");
         if (overflow) *overflow = (int)flag;
     }
-    if (x_s) pool_release(ctx, x_s);
-    if (y_s) pool_release(ctx, y_s);
-    if (r_s) pool_release(ctx, r_s);
     for (void* p_ : tmp.dev_allocs) (void)hipFree(p_);
     return rc;
 }
@@ -355,8 +351,8 @@ int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, in
         HIPCHK(ctx, launch_pool_pad(d_in, d_out, C, D, H, W, dil, pad, dims, mean, false, ctx->stream));
     } else {
         // (cells are [c / 8][D * H * W]: a volume converts as an image of D * H rows)
-        float* x_s = (float*)pool_alloc(ctx, split_cells(C) * 8 * (size_t)D * H * W * 4);
-        float* y_s = (float*)pool_alloc(ctx, split_cells(C) * 8 * (size_t)Do * Ho * Wo * 4);
+        const WorkBuf xb(ctx, split_cells(C) * 8 * (size_t)D * H * W * 4), yb(ctx, split_cells(C) * 8 * (size_t)Do * Ho * Wo * 4);
+        float *x_s = xb.as<float>(), *y_s = yb.as<float>();
         if (!x_s || !y_s) rc = fail(ctx, "out of device memory");
         if (!rc) {
             hipError_t e = flag_clear(ctx);
@@ -368,8 +364,6 @@ int tpz_pool(tpz_ctx* ctx, int op, int dims, const float* d_in, int C, int D, in
         unsigned flag = 0;
         if (flag_read(ctx, &flag) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");
         if (!rc && overflow) *overflow = (int)flag;
-        if (x_s) pool_release(ctx, x_s);
-        if (y_s) pool_release(ctx, y_s);
         return rc;
     }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, "tpz_pool: kernel failed");

@@ -22,6 +22,12 @@
 //   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
 //   rt_prefilter.hip  denoise pre-filters: fp64 low-pass GEMMs, tile covariances, the per-tile deconvolution filter (kernels there too)
 //   rt_resample.hip   the truncated-DFT resampler: plans with device-resident operators over the fp32-MFMA GEMM of resample_gemm.h
+// Workspace ownership: temporary device memory is held by a WorkBuf (below), never by a bare pointer.  The handle takes its buffer
+// from the pool that is current at that moment and remembers THAT pool, so its release -- scope exit, or release() where a
+// buffer must go back earlier -- finds the buffer whatever lane_enter / rec_select have made current since.  A handle lives
+// where the buffer is needed (per tile, per patch, per driver call) and no longer: the next request reuses what was released.
+// Closures given to enqueue() capture the raw pointer (buf.as<T>() copied into a local), never the handle: in a batched pass
+// they run at rec_flush, after the handle is gone, on a buffer nothing else takes from its per-image pool until then.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -209,8 +215,27 @@ int fail(tpz_ctx* ctx, const char* fmt, ...);
     } while (0)
 
 // ---- rt_core.hip
-void* pool_alloc(tpz_ctx* ctx, size_t bytes);
-void pool_release(tpz_ctx* ctx, void* p);
+// A temporary device buffer from the workspace pool that is current when it is taken (*ctx->pool_cur), held for the handle's
+// scope (ownership rule: the header comment above).  Move-only; an out-of-memory handle tests false.
+class WorkBuf {
+public:
+    WorkBuf() = default;
+    WorkBuf(tpz_ctx* ctx, size_t bytes);
+    WorkBuf(WorkBuf&& o) noexcept : pool_(o.pool_), p_(o.p_) { o.p_ = nullptr; }
+    WorkBuf& operator=(WorkBuf&& o) noexcept {
+        if (this != &o) { release(); pool_ = o.pool_; p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~WorkBuf() { release(); }
+    void release();                                  // marks the buffer unused in the pool it came from; idempotent
+    explicit operator bool() const { return p_ != nullptr; }
+    template <class T>
+    T* as() const { return static_cast<T*>(p_); }
+
+private:
+    std::vector<tpz_ctx::Buf>* pool_ = nullptr;      // (a member of the ctx: its address is stable)
+    void* p_ = nullptr;
+};
 hipError_t flag_clear(tpz_ctx* ctx);       // the f16-range overflow flag of a 2xf16 pass (d_flag): zero it on the ctx stream ...
 // ... copy it back, wait for the stream and return it in *flag.  The error is the copy's, else the wait's; check_copy = false: the
 // wait's alone (tpz_conv_split_2d, which checks none of its launches)
@@ -367,11 +392,9 @@ struct Slot {
     int C = 0, D = 1, H = 0, W = 0;
     long long cs = 0, ps = 0;
     int pitch = 0;
-    bool owned = false;
     bool set = false;
     bool split = false;       // p holds split f16 cells (split_fmt.h) instead of fp32 planes
     bool pooled = false;      // the producing conv already applied the max-pool that follows it (EPI_POOL)
-    float* alt = nullptr;     // the same tensor converted to the other format for a consumer that needs it
 };
 
 static void set_dense(Slot& s, float* p, int C, int D, int H, int W) {

@@ -19,28 +19,20 @@ int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims
     // always holds is one pick per pixel; keys are only ever touched up to the pick count
     size_t kcap = 4096;
     while (kcap < n) kcap <<= 1;
-    uint8_t* status = (uint8_t*)pool_alloc(ctx, n);
-    uint32_t* listA = (uint32_t*)pool_alloc(ctx, n * sizeof(uint32_t));
-    uint32_t* listB = (uint32_t*)pool_alloc(ctx, n * sizeof(uint32_t));
-    uint32_t* listV = (uint32_t*)pool_alloc(ctx, n * sizeof(uint32_t));
-    uint64_t* keys = (uint64_t*)pool_alloc(ctx, kcap * sizeof(uint64_t));
-    int* d_aux = (int*)pool_alloc(ctx, std::max(1, n_aux + n_aux2) * sizeof(int));
-    auto done = [&](int code) {
-        pool_release(ctx, status);
-        pool_release(ctx, listA);
-        pool_release(ctx, listB);
-        pool_release(ctx, listV);
-        pool_release(ctx, keys);
-        pool_release(ctx, d_aux);
-        return code;
-    };
-    if (!status || !listA || !listB || !listV || !keys || !d_aux) return done(fail(ctx, "nms: out of device memory"));
+    const WorkBuf status_b(ctx, n), listA_b(ctx, n * sizeof(uint32_t)), listB_b(ctx, n * sizeof(uint32_t)),
+        listV_b(ctx, n * sizeof(uint32_t)), keys_b(ctx, kcap * sizeof(uint64_t)),
+        aux_b(ctx, std::max(1, n_aux + n_aux2) * sizeof(int));
+    uint8_t* status = status_b.as<uint8_t>();
+    uint32_t *listA = listA_b.as<uint32_t>(), *listB = listB_b.as<uint32_t>(), *listV = listV_b.as<uint32_t>();
+    uint64_t* keys = keys_b.as<uint64_t>();
+    int* d_aux = aux_b.as<int>();
+    if (!status || !listA || !listB || !listV || !keys || !d_aux) return fail(ctx, "nms: out of device memory");
     int rc = 0;
     unsigned int* cnt = ctx->d_counters;
     prof_begin(ctx, 3, 0);
     auto bail = [&](const char* what, hipError_t e) {
         prof_end(ctx);
-        return done(fail(ctx, "nms: %s failed: %s", what, hipGetErrorString(e)));
+        return fail(ctx, "nms: %s failed: %s", what, hipGetErrorString(e));
     };
     hipError_t e = hipMemsetAsync(cnt, 0, NMS_COUNTERS * sizeof(unsigned int), s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_aux, h_aux, (n_aux + n_aux2) * sizeof(int), hipMemcpyHostToDevice, s);
@@ -74,7 +66,7 @@ int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims
         const unsigned int remaining = hc[NMS_BATCH];
         if (remaining == 0) break;
         if (first_batch) { ncand = hc[0]; first_batch = false; }
-        if (sweeps > 2ull * ncand + NMS_BATCH) { prof_end(ctx); return done(fail(ctx, "nms: fix-point did not converge")); }
+        if (sweeps > 2ull * ncand + NMS_BATCH) { prof_end(ctx); return fail(ctx, "nms: fix-point did not converge"); }
         // next batch: the leftovers are list [NMS_BATCH] -> restart the chain at [0] with that length
         hint = remaining;
         e = hipMemcpyAsync(cnt, cnt + NMS_BATCH, sizeof(unsigned int), hipMemcpyDeviceToDevice, s);
@@ -83,7 +75,7 @@ int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims
         if (e != hipSuccess) return bail("sweep chain reset", e);
     }
     if (npicks > 0) {
-        if ((size_t)npicks > kcap) { prof_end(ctx); return done(fail(ctx, "nms: pick list overflow")); }
+        if ((size_t)npicks > kcap) { prof_end(ctx); return fail(ctx, "nms: pick list overflow"); }
         size_t sp2 = 4096;
         while (sp2 < npicks) sp2 <<= 1;
         e = fill_u64(keys, npicks, sp2, 0ull, s);
@@ -96,7 +88,7 @@ int nms_common(tpz_ctx* ctx, const float* d_score, int D, int H, int W, int dims
     prof_end(ctx);
     if (h_n) *h_n = (int)npicks;
     if ((long long)npicks > (long long)cap) rc = fail(ctx, "nms: %u picks exceed the output capacity %d", npicks, cap);
-    return done(rc);
+    return rc;
 }
 
 }  // namespace

@@ -151,18 +151,17 @@ int tpz_particle_stack(tpz_ctx* ctx, const float* d_img, int mz, int H, int W, c
     if (n == 0) return 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t frame_s = (size_t)S * S, frames = (size_t)n * mz;
-    int* d_xy = (int*)pool_alloc(ctx, (size_t)n * 2 * sizeof(int));
-    float* d_ops = rs ? (float*)pool_alloc(ctx, (size_t)4 * S * R * sizeof(float)) : nullptr;
-    float* d_crop = rs ? (float*)pool_alloc(ctx, frames * frame_s * sizeof(float)) : nullptr;
-    float* d_p = rs ? (float*)pool_alloc(ctx, frames * 2 * S * R * sizeof(float)) : nullptr;
-    auto release = [&]() {
-        for (void* p : {(void*)d_xy, (void*)d_ops, (void*)d_crop, (void*)d_p})
-            if (p) pool_release(ctx, p);
-    };
-    if (!d_xy || (rs && (!d_ops || !d_crop || !d_p))) {
-        release();
-        return fail(ctx, "tpz_particle_stack: out of device memory for %d particles", n);
+    const WorkBuf xy_b(ctx, (size_t)n * 2 * sizeof(int));
+    WorkBuf ops_b, crop_b, p_b;
+    if (rs) {
+        ops_b = WorkBuf(ctx, (size_t)4 * S * R * sizeof(float));
+        crop_b = WorkBuf(ctx, frames * frame_s * sizeof(float));
+        p_b = WorkBuf(ctx, frames * 2 * S * R * sizeof(float));
     }
+    int* d_xy = xy_b.as<int>();
+    float *d_ops = ops_b.as<float>(), *d_crop = crop_b.as<float>(), *d_p = p_b.as<float>();
+    if (!d_xy || (rs && (!d_ops || !d_crop || !d_p)))
+        return fail(ctx, "tpz_particle_stack: out of device memory for %d particles", n);
     hipError_t e = hipMemcpyAsync(d_xy, h_xy, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && rs) e = hipMemcpyAsync(d_ops, h_ops, (size_t)4 * S * R * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     // 1. crop + standardise: reads the in-bounds boxes twice and writes them once
@@ -191,7 +190,6 @@ int tpz_particle_stack(tpz_ctx* ctx, const float* d_img, int mz, int H, int W, c
                 return hipGetLastError();
             });
     }
-    release();
     HIPCHK(ctx, e);
     return 0;
 }

@@ -195,19 +195,12 @@ int tpz_lowpass_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const double* 
         return fail(ctx, "tpz_lowpass_2d: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nqh = (size_t)H * rh, nqw = (size_t)W * rw;
-    double* d_qh = (double*)pool_alloc(ctx, nqh * sizeof(double));
-    double* d_qw = (double*)pool_alloc(ctx, nqw * sizeof(double));
-    double* d_t1 = (double*)pool_alloc(ctx, (size_t)rh * W * sizeof(double));
-    double* d_t2 = (double*)pool_alloc(ctx, (size_t)rh * rw * sizeof(double));
-    double* d_t3 = (double*)pool_alloc(ctx, (size_t)H * rw * sizeof(double));
-    auto release = [&]() {
-        for (void* p : {(void*)d_qh, (void*)d_qw, (void*)d_t1, (void*)d_t2, (void*)d_t3})
-            if (p) pool_release(ctx, p);
-    };
-    if (!d_qh || !d_qw || !d_t1 || !d_t2 || !d_t3) {
-        release();
+    const WorkBuf qh_b(ctx, nqh * sizeof(double)), qw_b(ctx, nqw * sizeof(double)), t1_b(ctx, (size_t)rh * W * sizeof(double)),
+        t2_b(ctx, (size_t)rh * rw * sizeof(double)), t3_b(ctx, (size_t)H * rw * sizeof(double));
+    double *d_qh = qh_b.as<double>(), *d_qw = qw_b.as<double>(), *d_t1 = t1_b.as<double>(), *d_t2 = t2_b.as<double>(),
+           *d_t3 = t3_b.as<double>();
+    if (!d_qh || !d_qw || !d_t1 || !d_t2 || !d_t3)
         return fail(ctx, "tpz_lowpass_2d: out of device memory for a %d x %d image", H, W);
-    }
     hipError_t e = hipMemcpyAsync(d_qh, h_qh, nqh * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_qw, h_qw, nqw * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     // y = Qh (Qh^T x Qw) Qw^T: 1. T1 = Qh^T x  2. T2 = T1 Qw  3. T3 = Qh T2  4. y = T3 Qw^T (rounded to fp32)
@@ -228,7 +221,6 @@ int tpz_lowpass_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const double* 
         e = enqueue(ctx, 2, 2.0 * h * rw * w, "lowpass_gemm", 8.0 * (h * rw + nqw) + 4.0 * h * w, [&](hipStream_t s) {
             return launch_lp_gemm((const double*)d_t3, rw, 1, (const double*)d_qw, 1, rw, d_out, H, W, rw, s);
         });
-    release();
     HIPCHK(ctx, e);
     return 0;
 }
@@ -244,13 +236,9 @@ int tpz_spatial_cov_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int 
     const int nrb = (ch_max + CV_ROWS - 1) / CV_ROWS;
     const long long nblk = (long long)P * P * nrb;
     if (nblk >= (1LL << 31)) return fail(ctx, "tpz_spatial_cov_2d: image too large");
-    double* d_part = (double*)pool_alloc(ctx, (size_t)nblk * CV_LAGS * sizeof(double));
-    double* d_cov = (double*)pool_alloc(ctx, (size_t)P * P * CV_LAGS * sizeof(double));
-    if (!d_part || !d_cov) {
-        if (d_part) pool_release(ctx, d_part);
-        if (d_cov) pool_release(ctx, d_cov);
-        return fail(ctx, "tpz_spatial_cov_2d: out of device memory");
-    }
+    const WorkBuf part_b(ctx, (size_t)nblk * CV_LAGS * sizeof(double)), cov_b(ctx, (size_t)P * P * CV_LAGS * sizeof(double));
+    double *d_part = part_b.as<double>(), *d_cov = cov_b.as<double>();
+    if (!d_part || !d_cov) return fail(ctx, "tpz_spatial_cov_2d: out of device memory");
     hipError_t e = enqueue(ctx, 2, 2.0 * CV_LAGS * H * W, "spatial_cov_partial", 4.0 * H * W, [&](hipStream_t s) {
         hipLaunchKernelGGL(cov_partial_kernel, dim3((unsigned)nblk), dim3(CV_THREADS), 0, s, d_x, H, W, P, nrb, d_part);
         return hipGetLastError();
@@ -263,8 +251,6 @@ int tpz_spatial_cov_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int 
         });
     if (e == hipSuccess) e = hipMemcpyAsync(h_cov, d_cov, (size_t)P * P * CV_LAGS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    pool_release(ctx, d_part);
-    pool_release(ctx, d_cov);
     HIPCHK(ctx, e);
     return 0;
 }
@@ -274,7 +260,8 @@ int tpz_tile_filter_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int 
     if (int rc = check_tiles(ctx, "tpz_tile_filter_2d", H, W, P, width)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nw = (size_t)P * P * CV_LAGS;
-    float* d_w = (float*)pool_alloc(ctx, nw * sizeof(float));
+    const WorkBuf w_b(ctx, nw * sizeof(float));
+    float* d_w = w_b.as<float>();
     if (!d_w) return fail(ctx, "tpz_tile_filter_2d: out of device memory");
     hipError_t e = hipMemcpyAsync(d_w, h_w, nw * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
@@ -283,7 +270,6 @@ int tpz_tile_filter_2d(tpz_ctx* ctx, const float* d_x, int H, int W, int P, int 
             hipLaunchKernelGGL(tile_filter_kernel, grid, dim3(TF_TILE * TF_TILE), 0, s, d_x, H, W, P, (const float*)d_w, d_out);
             return hipGetLastError();
         });
-    pool_release(ctx, d_w);
     HIPCHK(ctx, e);
     return 0;
 }

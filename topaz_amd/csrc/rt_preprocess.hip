@@ -182,7 +182,8 @@ int tpz_order_stats(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h
             return fail(ctx, "tpz_order_stats: rank %lld is outside [0, %zu)", h_ranks[j], n);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t hist_words = 1 + (size_t)OS_MAX_RANKS * OS_BINS;
-    unsigned long long* d_hist = (unsigned long long*)pool_alloc(ctx, hist_words * sizeof(unsigned long long));
+    const WorkBuf hist_b(ctx, hist_words * sizeof(unsigned long long));
+    unsigned long long* d_hist = hist_b.as<unsigned long long>();
     if (!d_hist) return fail(ctx, "tpz_order_stats: workspace allocation failed");
     std::vector<unsigned long long> h(hist_words);
     unsigned prefix[OS_MAX_RANKS];
@@ -222,7 +223,6 @@ int tpz_order_stats(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h
             prefix[j] = (prefix[j] << 8) | (unsigned)b;
         }
     }
-    pool_release(ctx, d_hist);
     HIPCHK(ctx, e);
     for (int j = 0; j < k; ++j) h_out[j] = has_nan ? NAN : key_value(prefix[j]);
     return 0;
@@ -235,7 +235,9 @@ int tpz_gather_f32(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h_
             return fail(ctx, "tpz_gather_f32: index %lld (position %zu) is outside [0, %zu)", h_idx[i], i, n);
     if (m == 0) return 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    long long* d_idx = (long long*)pool_alloc(ctx, m * sizeof(long long));
+    // (the index buffer goes back to the pool of this stream: whatever takes it next is queued behind the gather)
+    const WorkBuf idx_b(ctx, m * sizeof(long long));
+    long long* d_idx = idx_b.as<long long>();
     if (!d_idx) return fail(ctx, "tpz_gather_f32: workspace allocation failed");
     hipError_t e = hipMemcpyAsync(d_idx, h_idx, m * sizeof(long long), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -244,8 +246,6 @@ int tpz_gather_f32(tpz_ctx* ctx, const float* d_x, size_t n, const long long* h_
         e = hipGetLastError();
         prof_end(ctx);
     }
-    // (the index buffer goes back to the pool of this stream: whatever takes it next is queued behind the gather)
-    pool_release(ctx, d_idx);
     HIPCHK(ctx, e);
     return 0;
 }
@@ -283,7 +283,8 @@ int tpz_gmm_fit_fused(tpz_ctx* ctx, const float* d_x, size_t n, const double* pi
     const int blocks = grid_1d(n, GMM_BLOCKS);
     const size_t n_groups = (fits.size() + GMM_G - 1) / GMM_G;
     const size_t part_words = std::max<size_t>(n_groups, 1) * GMM_BLOCKS * GMM_G * 7, out_words = std::max<size_t>(fits.size(), 1) * 7;
-    double* d_buf = (double*)pool_alloc(ctx, (part_words + out_words + 8) * sizeof(double));
+    const WorkBuf buf_b(ctx, (part_words + out_words + 8) * sizeof(double));
+    double* d_buf = buf_b.as<double>();
     if (!d_buf) return fail(ctx, "tpz_gmm_fit_fused: workspace allocation failed");
     double *d_part = d_buf, *d_out = d_buf + part_words, *d_par = d_out + out_words;
     std::vector<double> S(out_words);
@@ -384,7 +385,6 @@ int tpz_gmm_fit_fused(tpz_ctx* ctx, const float* d_x, size_t n, const double* pi
             pis_out[f.i] = f.pi;
         }
     }
-    pool_release(ctx, d_buf);
     if (n_passes) *n_passes = passes;
     if (e != hipSuccess) return fail(ctx, "tpz_gmm_fit_fused: device pass failed: %s", hipGetErrorString(e));
     return 0;

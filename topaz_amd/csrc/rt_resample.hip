@@ -81,7 +81,8 @@ int tpz_resample_run(tpz_resample* pl, const float* d_in, float* d_out) {
     tpz_ctx* ctx = pl->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int M = pl->M, N = pl->N, m = pl->m, n = pl->n;
-    float* d_u = (float*)pool_alloc(ctx, (size_t)2 * m * pl->ldu * sizeof(float));
+    const WorkBuf u_b(ctx, (size_t)2 * m * pl->ldu * sizeof(float));       // (re-used only by later work on the same stream)
+    float* d_u = u_b.as<float>();
     if (!d_u) return fail(ctx, "tpz_resample_run: out of device memory for the %d x %d intermediate", 2 * m, N);
     RsArgs s1{};
     s1.seg[0].A = pl->d_L; s1.seg[0].B = d_in; s1.seg[0].K = M;
@@ -96,7 +97,6 @@ int tpz_resample_run(tpz_resample* pl, const float* d_in, float* d_out) {
     if (e == hipSuccess)
         e = enqueue(ctx, 2, 2.0 * dm * 2.0 * dN * dn, "resample_gemm", 4.0 * (2.0 * dm * dN + 2.0 * dN * dn + dm * dn),
                     [s2](hipStream_t s) { return launch_resample_gemm(s2, s); });
-    pool_release(ctx, d_u);       // (re-used only by later work on the same stream)
     HIPCHK(ctx, e);
     return 0;
 }

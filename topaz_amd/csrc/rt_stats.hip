@@ -59,9 +59,9 @@ int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, con
     if (!ctx || !d_x || !pis || !splits || !mus || !stds || !pis_out || !logps || n < 2 || n_init < 1)
         return fail(ctx, "tpz_gmm_fit: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    double *d_par = nullptr, *d_out = nullptr;
-    HIPCHK(ctx, hipMalloc((void**)&d_par, 8 * sizeof(double)));
-    if (hipMalloc((void**)&d_out, 8 * sizeof(double)) != hipSuccess) { (void)hipFree(d_par); return fail(ctx, "hipMalloc failed"); }
+    const WorkBuf par_b(ctx, 8 * sizeof(double)), out_b(ctx, 8 * sizeof(double));
+    double *d_par = par_b.as<double>(), *d_out = out_b.as<double>();
+    if (!d_par || !d_out) return fail(ctx, "tpz_gmm_fit: workspace allocation failed");
     int rc = 0;
     const double N = (double)n;
     auto pass = [&](int mode, const double (&par)[6], double (&S)[7]) -> int {
@@ -114,8 +114,6 @@ int tpz_gmm_fit(tpz_ctx* ctx, const float* d_x, size_t n, const double* pis, con
         stds[i] = std::sqrt(var);
         pis_out[i] = pi;
     }
-    (void)hipFree(d_par);
-    (void)hipFree(d_out);
     return rc;
 }
 

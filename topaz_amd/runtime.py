@@ -92,6 +92,13 @@ class Context:
         """kernel launches issued on this context so far (convolutions and elementwise)"""
         return int(self.lib.tpz_prof_launches(self.handle))
 
+    def pool_stats(self) -> dict:
+        """workspace buffers cached by all pools of this context (ctx, lane and batched-pass pools), their bytes, and how many
+        are marked in use -- 0 between calls"""
+        n, b, u = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(self.lib.tpz_ctx_pool_stats(self.handle, C.byref(n), C.byref(b), C.byref(u)), self.handle)
+        return {'buffers': n.value, 'bytes': b.value, 'buffers_in_use': u.value}
+
     def set_roi(self, on: bool = True) -> None:
         """patch windows of tpz_denoise_2d: each layer of a patch computes only what the kept centre depends on (default on)"""
         check(self.lib.tpz_ctx_set_roi(self.handle, 1 if on else 0), self.handle)
