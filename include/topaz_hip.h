@@ -391,6 +391,23 @@ int tpz_ctx_set_batch(tpz_ctx* ctx, int n);
 int tpz_ctx_set_batch_memory(tpz_ctx* ctx, long long bytes);
 long long tpz_prof_launches(tpz_ctx* ctx);
 int tpz_ctx_pool_stats(tpz_ctx* ctx, long long* buffers, long long* bytes, long long* buffers_in_use);
+/* Poisoned workspace, for tests (default off; with TPZ_DEBUG=1: TPZ_POISON=1).  The workspace pools hand the same buffers to the
+ * same sequence of requests and never clear them, so a cell that a kernel fails to write reads back as what the previous run left
+ * there.  on = 1: every temporary buffer the library takes is filled whole (its size in the pool, whole MiB) with 0xFF bytes before
+ * anything can touch it -- every f16 / f32 / f64 a NaN, every 64-bit key the maximum, every int -1 --, ordered on the stream (or in
+ * the recorded batch) that orders the consumer's launches.  The fills count neither in tpz_prof_launches nor in the profiler.
+ * tpz_ctx_poison_stats: whether the switch is on, the fills made and the bytes filled since the context was created; any out
+ *   pointer may be NULL.
+ * tpz_ctx_walk_stats: the 2xf16 conv launches issued since the context was created, by tile walk: out[0] one workgroup per tile
+ *   in row-major / XCD order, [1] the patch raster, [2] persistent workgroups, [3] the weights-resident kernel, [4] the batched grid
+ *   of several images.
+ * tpz_debug_workspace_peek: takes a temporary buffer of `bytes` from the context's pool as a driver would, waits for the stream,
+ *   copies the buffer's first `bytes` rounded up to a whole MiB to host_out (which must have that much room) and gives the buffer
+ *   back: what a kernel would find there. */
+int tpz_ctx_set_poison(tpz_ctx* ctx, int on);
+int tpz_ctx_poison_stats(tpz_ctx* ctx, int* on, long long* fills, long long* bytes);
+int tpz_ctx_walk_stats(tpz_ctx* ctx, long long out[5]);
+int tpz_debug_workspace_peek(tpz_ctx* ctx, size_t bytes, void* host_out);
 /* Patch windows: a patch of tpz_denoise_2d keeps only its centre (topaz/denoise.py:299-323: patch_size pixels of a
  * patch_size + 2*padding tile), so each layer computes only the rectangle of its tensor that those pixels depend on (the
  * U-Net's receptive field is ~230 pixels, the CLI's default padding 500).  The statistics of the normalisation are still the

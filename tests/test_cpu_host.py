@@ -50,18 +50,19 @@ def test_stray_debug_variables_change_nothing_without_TPZ_DEBUG(monkeypatch):
     from topaz_amd import _lib
     lib = _lib.load_library()
     buf = C.create_string_buffer(512)
-    for k in ('TPZ_DEBUG', 'TPZ_EXACT_FP32', 'TPZ_NO_ROI', 'TPZ_NO_RANGE', 'TPZ_NO_WIDEN', 'TPZ_BATCH', 'TPZ_LANES'):
+    for k in ('TPZ_DEBUG', 'TPZ_EXACT_FP32', 'TPZ_NO_ROI', 'TPZ_NO_RANGE', 'TPZ_NO_WIDEN', 'TPZ_BATCH', 'TPZ_LANES',
+              'TPZ_POISON'):
         monkeypatch.delenv(k, raising=False)
     assert lib.tpz_debug_switches(buf, 512) == 0 and buf.value == b''
     for k, v in (('TPZ_EXACT_FP32', '1'), ('TPZ_NO_ROI', '1'), ('TPZ_NO_RANGE', '1'), ('TPZ_NO_WIDEN', '1'), ('TPZ_BATCH', '2'),
-                 ('TPZ_LANES', '3')):
+                 ('TPZ_LANES', '3'), ('TPZ_POISON', '1')):
         monkeypatch.setenv(k, v)
     assert lib.tpz_debug_switches(buf, 512) == 0 and buf.value == b'', buf.value      # stray variables: nothing in effect
     monkeypatch.setenv('TPZ_DEBUG', '0')
     assert lib.tpz_debug_switches(buf, 512) == 0
     monkeypatch.setenv('TPZ_DEBUG', '1')
-    assert lib.tpz_debug_switches(buf, 512) == 6
-    assert buf.value.split() == [b'exact_fp32', b'no_roi', b'no_range', b'no_widen', b'batch', b'lanes']
+    assert lib.tpz_debug_switches(buf, 512) == 7
+    assert buf.value.split() == [b'exact_fp32', b'no_roi', b'no_range', b'no_widen', b'batch', b'lanes', b'poison']
     # and no other getenv in the device library's sources
     import glob, os, re
     root = os.path.dirname(os.path.abspath(_lib.__file__))

@@ -122,6 +122,10 @@ _SIGNATURES = {
     'tpz_ctx_set_tiling': (C.c_int, [_P, C.c_longlong, C.c_int]),
     'tpz_prof_launches': (C.c_longlong, [_P]),
     'tpz_ctx_pool_stats': (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    'tpz_ctx_set_poison': (C.c_int, [_P, C.c_int]),
+    'tpz_ctx_poison_stats': (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    'tpz_ctx_walk_stats': (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    'tpz_debug_workspace_peek': (C.c_int, [_P, C.c_size_t, _P]),
     'tpz_ctx_set_roi': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_rw': (C.c_int, [_P, C.c_int]),
     'tpz_ctx_set_persist': (C.c_int, [_P, C.c_int, C.c_int]),

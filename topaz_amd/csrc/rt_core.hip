@@ -70,6 +70,7 @@ DebugEnv debug_env() {
     d.no_pool3d = flag("TPZ_NO_POOL3D");
     d.no_fold = flag("TPZ_NO_FOLD");
     d.no_widen = flag("TPZ_NO_WIDEN");
+    d.poison = flag("TPZ_POISON");
     if (flag("TPZ_NO_BATCH")) d.batch = 0;
     else if (const char* e = getenv("TPZ_BATCH")) {
         const int n = atoi(e);
@@ -90,8 +91,8 @@ int fail(tpz_ctx* ctx, const char* fmt, ...) {
     return 1;
 }
 
-// a buffer of at least `bytes` from `pool`, marked used: the smallest cached one that fits, else a new one
-static void* pool_alloc(tpz_ctx* ctx, std::vector<tpz_ctx::Buf>& pool, size_t bytes) {
+// a buffer of at least `bytes` from `pool`, marked used: the smallest cached one that fits, else a new one; *size: its whole size
+static void* pool_alloc(tpz_ctx* ctx, std::vector<tpz_ctx::Buf>& pool, size_t bytes, size_t* size) {
     if (bytes == 0) bytes = 16;
     int best = -1;
     for (int i = 0; i < (int)pool.size(); ++i) {
@@ -100,6 +101,7 @@ static void* pool_alloc(tpz_ctx* ctx, std::vector<tpz_ctx::Buf>& pool, size_t by
     }
     if (best >= 0) {
         pool[best].used = true;
+        *size = pool[best].bytes;
         return pool[best].p;
     }
     void* p = nullptr;
@@ -138,9 +140,29 @@ static void* pool_alloc(tpz_ctx* ctx, std::vector<tpz_ctx::Buf>& pool, size_t by
         }
     }
     pool.push_back({p, rounded, true});
+    *size = rounded;
     return p;
 }
-WorkBuf::WorkBuf(tpz_ctx* ctx, size_t bytes) : pool_(ctx->pool_cur), p_(pool_alloc(ctx, *ctx->pool_cur, bytes)) {}
+// tpz_ctx_set_poison: 0xFF over the whole buffer, ordered ahead of whatever the new holder launches -- on the current stream (the
+// ctx stream or the lane's that lane_enter made current), or as a recorded op of the current image of a batched pass, which
+// rec_flush replays in its place in that image's list.  Not a launch of the ledger (n_launches) and not timed by the profiler.
+static void poison_fill(tpz_ctx* ctx, void* p, size_t size) {
+    ++ctx->n_poison_fills;
+    ctx->poison_bytes += (long long)size;
+    if (ctx->rec_on) {
+        RecOp op;
+        op.fn = [=](hipStream_t st) { return hipMemsetAsync(p, 0xFF, size, st); };
+        op.fill = true;
+        ctx->rec[ctx->rec_cur].push_back(std::move(op));
+        return;
+    }
+    (void)hipMemsetAsync(p, 0xFF, size, ctx->stream);
+}
+WorkBuf::WorkBuf(tpz_ctx* ctx, size_t bytes) : pool_(ctx->pool_cur) {
+    size_t size = 0;
+    p_ = pool_alloc(ctx, *pool_, bytes, &size);
+    if (ctx->poison && p_) poison_fill(ctx, p_, size);
+}
 // (by device pointer, not by index: a trim of the pool erases entries)
 void WorkBuf::release() {
     if (p_)
@@ -299,6 +321,10 @@ int rec_flush(tpz_ctx* ctx) {
             auto& L = ctx->rec[i];
             while (cur[i] < L.size() && !L[cur[i]].ks && !rc) {
                 RecOp& op = L[cur[i]++];
+                if (op.fill) {                  // (a poison fill: no launch of the ledger)
+                    if (op.fn(ctx->stream) != hipSuccess) rc = fail(ctx, "poison fill failed");
+                    continue;
+                }
                 prof_begin(ctx, op.cls, op.flops, op.key, op.bytes);
                 const hipError_t e = op.fn(ctx->stream);
                 prof_end(ctx);
@@ -337,6 +363,7 @@ int rec_flush(tpz_ctx* ctx) {
         }
         prof_end(ctx);
         ++ctx->n_launches;
+        ++ctx->n_walk[m == 1 ? WALK_PLAIN : WALK_MULTI];
         ++n_issued;
         if (e != hipSuccess) rc = fail(ctx, "conv_split launch failed: %s", hipGetErrorString(e));
         for (int k = 0; k < m; ++k) ++cur[who[k]];
@@ -366,7 +393,7 @@ int tpz_debug_switches(char* buf, int buf_len) {
     add(d.no_roi, "no_roi"); add(d.no_persist, "no_persist"); add(d.trace_host, "trace_host"); add(d.no_range, "no_range");
     add(d.no_raster, "no_raster"); add(d.no_srcmajor, "no_srcmajor"); add(d.no_valu_last, "no_valu_last"); add(d.no_rw, "no_rw");
     add(d.no_pool3d, "no_pool3d"); add(d.no_fold, "no_fold"); add(d.no_widen, "no_widen"); add(d.batch >= 0, "batch");
-    add(d.lanes != 0, "lanes");
+    add(d.lanes != 0, "lanes"); add(d.poison, "poison");
     if (buf && buf_len > 0) snprintf(buf, (size_t)buf_len, "%s", s.c_str());
     return n;
 }
@@ -402,6 +429,7 @@ int tpz_ctx_create(int device_id, tpz_ctx** out) {
     ctx->range_scaling = !ctx->dbg.no_range;
     ctx->raster = !ctx->dbg.no_raster;
     ctx->exact = ctx->dbg.exact_fp32;
+    ctx->poison = ctx->dbg.poison;
     if (ctx->dbg.batch >= 0) ctx->batch = ctx->dbg.batch;
     if (ctx->dbg.lanes >= 2 && ctx->dbg.lanes <= N_LANES) ctx->n_lanes = ctx->dbg.lanes;
     if (hipStreamCreate(&ctx->own_stream) != hipSuccess) { delete ctx; return fail(nullptr, "hipStreamCreate failed"); }
@@ -496,6 +524,44 @@ int tpz_ctx_pool_stats(tpz_ctx* ctx, long long* buffers, long long* bytes, long 
     if (bytes) *bytes = b;
     if (buffers_in_use) *buffers_in_use = u;
     return 0;
+}
+
+int tpz_ctx_set_poison(tpz_ctx* ctx, int on) {
+    if (!ctx) return fail(nullptr, "ctx is NULL");
+    ctx->poison = on != 0;
+    return 0;
+}
+int tpz_ctx_poison_stats(tpz_ctx* ctx, int* on, long long* fills, long long* bytes) {
+    if (!ctx) return fail(nullptr, "ctx is NULL");
+    if (on) *on = ctx->poison ? 1 : 0;
+    if (fills) *fills = ctx->n_poison_fills;
+    if (bytes) *bytes = ctx->poison_bytes;
+    return 0;
+}
+int tpz_ctx_walk_stats(tpz_ctx* ctx, long long out[5]) {
+    if (!ctx || !out) return fail(ctx, "tpz_ctx_walk_stats: NULL argument");
+    static_assert(N_WALKS == 5, "tpz_ctx_walk_stats reports five walks");
+    for (int i = 0; i < N_WALKS; ++i) out[i] = ctx->n_walk[i];
+    return 0;
+}
+int tpz_debug_workspace_peek(tpz_ctx* ctx, size_t bytes, void* host_out) {
+    if (!ctx || !host_out) return fail(ctx, "tpz_debug_workspace_peek: NULL argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (bytes == 0) bytes = 16;
+    // every pool buffer is whole MiB: the copy covers the rounded request -- all of a new buffer, the head of a larger cached one
+    const size_t rounded = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
+    std::vector<tpz_ctx::Buf>* const saved = ctx->pool_cur;
+    ctx->pool_cur = &ctx->pool;
+    int rc = 0;
+    {
+        const WorkBuf buf(ctx, bytes);
+        if (!buf) rc = fail(ctx, "out of device memory");
+        else if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+                 hipMemcpy(host_out, buf.as<void>(), rounded, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(ctx, "tpz_debug_workspace_peek: copy failed");
+    }
+    ctx->pool_cur = saved;
+    return rc;
 }
 
 int tpz_ctx_set_persist(tpz_ctx* ctx, int mode, int workgroups) {

@@ -156,6 +156,9 @@ int denoise_3d_pass(tpz_model* m, const float* d_in, int D, int H, int W, int pa
     int rc = 0;
     auto inst_enter = [&](int inst) {
         if (batched) {
+            // (the lane's stream too: what a WorkBuf enqueues when it is taken, ahead of any batch, must run on the stream
+            // that this instance's batches will be issued on)
+            lane_enter(ctx, inst / per_lane);
             ctx->rec_cur = inst % per_lane;
             ctx->pool_cur = &ctx->rec_pools[inst / per_lane][inst % per_lane];
         } else lane_enter(ctx, inst);

@@ -177,6 +177,7 @@ int launch_rw(tpz_ctx* ctx, SplitArgs& a, int dil, int epi, double flops, const 
     const SplitArgs ac = a;
     hipError_t e = enqueue(ctx, 0, flops, names[di][epi], bytes, [=](hipStream_t st) { return launch_conv_rw(ac, dil, epi, wgs, st); });
     if (e != hipSuccess) return fail(ctx, "conv_rw launch failed: %s", hipGetErrorString(e));
+    ++ctx->n_walk[WALK_RW];          // (run_conv_split sends no layer here in a batched pass: the launch was issued)
     return 0;
 }
 
@@ -372,6 +373,7 @@ int launch_split(tpz_ctx* ctx, const SplitKernelInfo& ks, SplitArgs& a, int n_co
     hipError_t e = ks.launch(a, grid, ctx->stream);
     prof_end(ctx);
     ++ctx->n_launches;
+    ++ctx->n_walk[a.n_tiles > 0 ? WALK_PERSIST : a.xcd_swizzle == 2 ? WALK_RASTER : WALK_PLAIN];
     HIPCHK(ctx, e);
     return 0;
 }

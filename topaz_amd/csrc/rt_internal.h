@@ -70,6 +70,7 @@ struct DebugEnv {
     bool no_pool3d = false;      // TPZ_NO_POOL3D    no fused max-pool epilogue on 3-D encoder convs
     bool no_fold = false;        // TPZ_NO_FOLD      ResidA 1x1 projections as layers of their own
     bool no_widen = false;       // TPZ_NO_WIDEN     never load a program zero-padded to multiples of 16 channels
+    bool poison = false;         // TPZ_POISON       every workspace buffer is filled with 0xFF bytes when it is taken (tpz_ctx_set_poison)
     int batch = -1;              // TPZ_BATCH=n / TPZ_NO_BATCH=1 (0)   images per batched pass (tpz_ctx_set_batch); -1: default
     int lanes = 0;               // TPZ_LANES=n      patch lanes in use (tpz_ctx_set_lanes); 0: default
 };
@@ -83,6 +84,9 @@ static inline double host_now_ms() {
 #define TPZ_N_LANES 4
 #endif
 enum { N_LANES = TPZ_N_LANES };      // patch lanes: the most auxiliary streams the patches / tiles of an image alternate on
+// the tile walk of a 2xf16 conv launch (tpz_ctx::n_walk): one workgroup per tile in row-major / XCD order, the patch raster
+// (xcd_swizzle 2), persistent workgroups (MODE 4), the weights-resident kernel (conv_rw.h), the batched grid (conv_split_multi_kernel)
+enum { WALK_PLAIN = 0, WALK_RASTER, WALK_PERSIST, WALK_RW, WALK_MULTI, N_WALKS };
 enum { NMS_BATCH = 4, NMS_VER = 5, NMS_SNAP = 9, NMS_PICKS = 15, NMS_COUNTERS = 16 };
 
 struct ProfRec {
@@ -107,6 +111,7 @@ struct RecOp {
     int cls = 2;
     double flops = 0, bytes = 0;
     const void* key = nullptr;
+    bool fill = false;           // a poison fill (WorkBuf): replayed in its place, counted neither as a launch nor by the profiler
 };
 
 }  // namespace tpz::rt
@@ -174,6 +179,13 @@ struct tpz_ctx {
     bool range_scaling = true;                // tpz_ctx_set_range
     bool raster = true;                       // tpz_ctx_set_raster: patch raster of the 8-wave tiles' grids
     bool rw_enabled = true;                   // tpz_ctx_set_rw: the weights-resident kernel for 3x3 32 -> 32 layers (conv_rw.h)
+    // tpz_ctx_set_poison: a WorkBuf fills its whole pool buffer with 0xFF bytes when it takes it (every f16 / f32 / f64 a NaN, every
+    // uint64_t the maximum, every int -1), so that a cell no kernel writes, or one read before it is written, shows in the result
+    // instead of holding whatever the buffer's last tenant left -- often the right answer of the previous run
+    bool poison = false;
+    long long n_poison_fills = 0, poison_bytes = 0;      // tpz_ctx_poison_stats
+    // conv launches by tile walk since the ctx was created (tpz_ctx_walk_stats)
+    long long n_walk[tpz::rt::N_WALKS] = {0, 0, 0, 0, 0};
     // internal tiling of tpz_model_forward (run_image): 2-D images above tile_limit_px pixels are scored in tile_size^2 tiles
     long long tile_limit_px = 40LL << 20;
     int tile_size = 4096;
@@ -217,6 +229,8 @@ int fail(tpz_ctx* ctx, const char* fmt, ...);
 // ---- rt_core.hip
 // A temporary device buffer from the workspace pool that is current when it is taken (*ctx->pool_cur), held for the handle's
 // scope (ownership rule: the header comment above).  Move-only; an out-of-memory handle tests false.
+// Under tpz_ctx_set_poison the constructor fills the whole pool buffer (its rounded size) with 0xFF bytes ahead of every consumer:
+// on the stream that is current (a patch lane's included) or, in a batched pass, as a recorded op of the current image's list.
 class WorkBuf {
 public:
     WorkBuf() = default;

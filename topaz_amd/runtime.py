@@ -24,6 +24,8 @@ DEFAULT_BAR = 1e-4
 # The encodings a float32 result can leave the device in (tpz_encode, Stage.download_encoded) and the dtype each is stored as
 ENC_F16, ENC_U8 = _lib.TPZ_ENC_F16, _lib.TPZ_ENC_U8
 ENC_DTYPES = {ENC_F16: np.dtype(np.float16), ENC_U8: np.dtype(np.uint8)}
+# The tile walks Context.walk_stats() counts 2xf16 conv launches by, in the order of tpz_ctx_walk_stats
+WALKS = ('plain', 'raster', 'persistent', 'weights_resident', 'multi')
 
 
 class Context:
@@ -38,6 +40,7 @@ class Context:
         check(self.lib.tpz_ctx_create(self.device, C.byref(h)))
         self.handle = h
         self._bound_stream = None
+        self._poison = self.poison_stats()['on']        # (TPZ_DEBUG=1 TPZ_POISON=1: on from the start)
 
     def bind_current_stream(self) -> None:
         """run subsequent calls on torch's current stream for this device"""
@@ -98,6 +101,32 @@ class Context:
         n, b, u = C.c_longlong(), C.c_longlong(), C.c_longlong()
         check(self.lib.tpz_ctx_pool_stats(self.handle, C.byref(n), C.byref(b), C.byref(u)), self.handle)
         return {'buffers': n.value, 'bytes': b.value, 'buffers_in_use': u.value}
+
+    def set_poison(self, on: bool = True) -> None:
+        """poisoned workspace, for tests: every temporary buffer the library takes is filled whole with 0xFF bytes first, and the
+        result tensors this module allocates with NaN (_result), so that a cell nothing writes shows in the result (default off)"""
+        check(self.lib.tpz_ctx_set_poison(self.handle, 1 if on else 0), self.handle)
+        self._poison = bool(on)
+
+    def poison_stats(self) -> dict:
+        """whether the poison switch is on, the workspace fills made and the bytes filled since the context was created"""
+        on, n, b = C.c_int(), C.c_longlong(), C.c_longlong()
+        check(self.lib.tpz_ctx_poison_stats(self.handle, C.byref(on), C.byref(n), C.byref(b)), self.handle)
+        return {'on': bool(on.value), 'fills': n.value, 'bytes': b.value}
+
+    def walk_stats(self) -> dict:
+        """2xf16 conv launches since the context was created, by tile walk (tpz_ctx_walk_stats)"""
+        out = (C.c_longlong * 5)()
+        check(self.lib.tpz_ctx_walk_stats(self.handle, out), self.handle)
+        return dict(zip(WALKS, (int(v) for v in out)))
+
+    def workspace_peek(self, nbytes: int) -> np.ndarray:
+        """what a driver taking `nbytes` of workspace from the ctx pool would find: the buffer's first nbytes, rounded up to a
+        whole MiB, as uint8 (tpz_debug_workspace_peek)"""
+        self.bind_current_stream()
+        out = np.empty((max(int(nbytes), 1) + (1 << 20) - 1) >> 20 << 20, dtype=np.uint8)
+        check(self.lib.tpz_debug_workspace_peek(self.handle, int(nbytes), out.ctypes.data_as(C.c_void_p)), self.handle)
+        return out
 
     def set_roi(self, on: bool = True) -> None:
         """patch windows of tpz_denoise_2d: each layer of a patch computes only what the kept centre depends on (default on)"""
@@ -194,6 +223,15 @@ def get_context(device: Optional[int] = None) -> Context:
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
+
+
+def _result(ctx: Context, shape, dtype=torch.float32) -> torch.Tensor:
+    """an uninitialised tensor on the ctx device for a result the library stores straight into; under Context.set_poison it is
+    filled with NaN (integers: all ones) on the current stream first, as the library's own workspace is"""
+    y = torch.empty(tuple(shape), dtype=dtype, device=ctx.torch_device())
+    if ctx._poison:
+        y.fill_(float('nan') if dtype.is_floating_point else (255 if dtype == torch.uint8 else -1))
+    return y
 
 
 def as_device_f32(x, ctx: Context) -> torch.Tensor:
@@ -553,7 +591,7 @@ class DeviceModel:
         co = C.c_int(1)
         check(self.ctx.lib.tpz_model_out_channels(self.handle, C.byref(co)), self.ctx.handle)
         shape = (N, co.value, Do, Ho, Wo) if nd == 3 else (N, co.value, Ho, Wo)
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        y = _result(self.ctx, shape)
         check(self.ctx.lib.tpz_model_forward(self.handle, _ptr(x), N, D, H, W, _ptr(y)), self.ctx.handle)
         return y
 
@@ -561,7 +599,7 @@ class DeviceModel:
         self.ctx.bind_current_stream()
         x = as_device_f32(x, self.ctx)
         H, W = x.shape
-        y = torch.empty_like(x)
+        y = _result(self.ctx, x.shape)
         check(self.ctx.lib.tpz_denoise_2d(self.handle, _ptr(x), H, W, int(patch), int(pad), _ptr(y)), self.ctx.handle)
         return y
 
@@ -570,7 +608,7 @@ class DeviceModel:
         self.ctx.bind_current_stream()
         x = as_device_f32(x, self.ctx)
         D, H, W = x.shape
-        y = torch.empty_like(x) if n_shards == 1 else torch.zeros_like(x)
+        y = _result(self.ctx, x.shape) if n_shards == 1 else torch.zeros_like(x)
         check(self.ctx.lib.tpz_denoise_3d_shard(self.handle, _ptr(x), D, H, W, int(patch), int(pad), int(shard), int(n_shards),
                                                 _ptr(y)), self.ctx.handle)
         return y
@@ -605,7 +643,7 @@ def conv(x: torch.Tensor, weight, bias=None, dil: int = 1, pad: int = 0, slope: 
     Ho, Wo = H + 2 * pad - span, W + 2 * pad - span
     co = 1 if head_w is not None else cout
     shape = (co, Do, Ho, Wo) if dims == 3 else (co, Ho, Wo)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = _result(ctx, shape)
 
     def hp(a):
         if a is None:
@@ -640,7 +678,7 @@ def conv_split(x: torch.Tensor, weight, bias=None, dil: int = 1, pad: int = 0, s
     assert w.ndim == 4 and w.shape[1] == cin, (w.shape, cin)
     span = dil * (k - 1)
     Ho, Wo = H + 2 * pad - span, W + 2 * pad - span
-    y = torch.empty((1 if head_w is not None else cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    y = _result(ctx, (1 if head_w is not None else cout, Ho, Wo))
 
     def hp(a):
         if a is None:
@@ -720,7 +758,7 @@ def gather(x: torch.Tensor, idx, ctx: Optional[Context] = None) -> torch.Tensor:
     ctx.bind_current_stream()
     x = as_device_f32(x.reshape(-1), ctx)
     idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
-    y = torch.empty(len(idx), dtype=torch.float32, device=x.device)
+    y = _result(ctx, (len(idx),))
     check(ctx.lib.tpz_gather_f32(ctx.handle, _ptr(x), x.numel(), idx.ctypes.data_as(C.c_void_p), len(idx), _ptr(y)),
           ctx.handle)
     return y
@@ -732,7 +770,7 @@ def normalize_f64(x: torch.Tensor, mean: float, std: float, ctx: Optional[Contex
     ctx = ctx or get_context()
     ctx.bind_current_stream()
     x = as_device_f32(x, ctx)
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_normalize_f64(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), _ptr(y)), ctx.handle)
     return y
 
@@ -746,7 +784,7 @@ def maxpool2(x: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     D = x.shape[1] if dims == 3 else 1
     H, W = x.shape[-2], x.shape[-1]
     shape = (Cc, D // 2, H // 2, W // 2) if dims == 3 else (Cc, H // 2, W // 2)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = _result(ctx, shape)
     check(ctx.lib.tpz_maxpool2(ctx.handle, dims, _ptr(x), Cc, D, H, W, _ptr(y)), ctx.handle)
     return y
 
@@ -767,7 +805,7 @@ def pool(x: torch.Tensor, op: str = 'max', dil: int = 1, pad: int = 1, split: bo
     shape = (Cc, D + grow, H + grow, W + grow) if dims == 3 else (Cc, H + grow, W + grow)
     if min(shape) < 1:
         raise ValueError(f'input {tuple(x.shape)} is too small for a 3-tap pool at dilation {dil}, padding {pad}')
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = _result(ctx, shape)
     ovf = C.c_int(0)
     code = {'max': _lib.TPZ_OP_MAXPOOL, 'avg': _lib.TPZ_OP_AVGPOOL}[op]
     check(ctx.lib.tpz_pool(ctx.handle, code, dims, _ptr(x), Cc, D, H, W, int(dil), int(pad), 1 if split else 0, _ptr(y),
@@ -788,7 +826,7 @@ def affine(x: torch.Tensor, scale: float, shift: float, ctx: Optional[Context] =
     ctx = ctx or get_context()
     ctx.bind_current_stream()
     x = as_device_f32(x, ctx)
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_affine(ctx.handle, _ptr(x), x.numel(), float(scale), float(shift), _ptr(y)), ctx.handle)
     return y
 
@@ -798,7 +836,7 @@ def normalize(x: torch.Tensor, mean: float, std: float, ctx: Optional[Context] =
     ctx = ctx or get_context()
     ctx.bind_current_stream()
     x = as_device_f32(x, ctx)
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_normalize(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), _ptr(y)), ctx.handle)
     return y
 
@@ -816,7 +854,7 @@ def decode_stored(x: np.ndarray, ctx: Optional[Context] = None) -> torch.Tensor:
         raise _lib.TopazHipError(f'decode_stored: {x.dtype} is not a stored type the device decodes (int8, int16, uint16, '
                                  'float16)')
     raw = torch.from_numpy(x.reshape(-1).view(np.uint8)).to(ctx.torch_device())
-    y = torch.empty(x.shape, dtype=torch.float32, device=ctx.torch_device())
+    y = _result(ctx, x.shape)
     if x.size:
         check(ctx.lib.tpz_decode(ctx.handle, _ptr(raw), mode, x.size, _ptr(y)), ctx.handle)
     return y
@@ -837,7 +875,7 @@ def encode(x: torch.Tensor, enc: int, params=None, ctx: Optional[Context] = None
         x = as_device_f32(x, ctx)
     dtype = torch.float16 if enc == ENC_F16 else torch.uint8
     if out is None:
-        out = torch.empty(x.shape, dtype=dtype, device=x.device)
+        out = _result(ctx, x.shape, dtype)
     elif out.dtype != dtype or out.numel() < x.numel() or not out.is_contiguous():
         raise _lib.TopazHipError('encode: `out` must be a contiguous tensor of the stored dtype with room for every pixel')
     counter = torch.zeros(1, dtype=torch.int64, device=x.device) if count and enc == ENC_F16 else None
@@ -854,7 +892,7 @@ def normalize_cutoff(x: torch.Tensor, mean: float, std: float, cutoff: float, ct
     ctx = ctx or get_context()
     ctx.bind_current_stream()
     x = as_device_f32(x, ctx)
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_normalize_cutoff(ctx.handle, _ptr(x), x.numel(), float(mean), float(std), float(cutoff), _ptr(y)),
           ctx.handle)
     return y
@@ -866,7 +904,7 @@ def filter_2d(x: torch.Tensor, w, bias: float = 0.0, ctx: Optional[Context] = No
     x = as_device_f32(x, ctx)
     w = np.ascontiguousarray(np.asarray(w, dtype=np.float32))
     H, W = x.shape
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_filter_2d(ctx.handle, _ptr(x), H, W, w.ctypes.data_as(C.c_void_p), w.shape[-1], float(bias),
                                 _ptr(y)), ctx.handle)
     return y
@@ -881,7 +919,7 @@ def lowpass_2d(x: torch.Tensor, qh: np.ndarray, qw: np.ndarray, ctx: Optional[Co
     H, W = x.shape
     assert qh.dtype == np.float64 and qw.dtype == np.float64 and qh.flags.c_contiguous and qw.flags.c_contiguous
     assert qh.shape[0] == H and qw.shape[0] == W
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_lowpass_2d(ctx.handle, _ptr(x), H, W, qh.ctypes.data_as(C.c_void_p), qh.shape[1],
                                  qw.ctypes.data_as(C.c_void_p), qw.shape[1], _ptr(y)), ctx.handle)
     return y
@@ -907,7 +945,7 @@ def tile_filter_2d(x: torch.Tensor, w: np.ndarray, patch: int = 1, ctx: Optional
     H, W = x.shape
     w = np.ascontiguousarray(w, dtype=np.float32)
     assert w.shape == (patch * patch, w.shape[-1], w.shape[-1])
-    y = torch.empty_like(x)
+    y = _result(ctx, x.shape)
     check(ctx.lib.tpz_tile_filter_2d(ctx.handle, _ptr(x), H, W, int(patch), w.shape[-1], w.ctypes.data_as(C.c_void_p), _ptr(y)),
           ctx.handle)
     return y
@@ -926,7 +964,7 @@ def particle_stack(img: torch.Tensor, xy, size: int, resize: int = -1, ops: Opti
     n = xy.shape[0]
     R = int(resize) if resize > 0 else int(size)
     if out is None:
-        out = torch.empty((n, mz, R, R), dtype=torch.float32, device=img.device)
+        out = _result(ctx, (n, mz, R, R))
     assert out.is_contiguous() and out.numel() == n * mz * R * R
     if ops is not None:
         ops = np.ascontiguousarray(ops, dtype=np.float32)
@@ -948,8 +986,8 @@ def nms(score: torch.Tensor, r: int, threshold: float, scale: float = 1.0, ctx: 
         # a pick suppresses at least itself; with r >= 1 picks are > r apart, so this bound is generous
         cap = n_el if r < 1 else max(1024, min(n_el, (4 * n_el) // max(1, r * r) + 1024))
     while True:
-        coords = torch.empty((cap, dims), dtype=torch.int32, device=score.device)
-        out = torch.empty((cap,), dtype=torch.float32, device=score.device)
+        coords = _result(ctx, (cap, dims), torch.int32)
+        out = _result(ctx, (cap,))
         n = C.c_int(0)
         thr = float(threshold)
         if thr == float('-inf'):
@@ -997,7 +1035,7 @@ class ResamplePlan:
             raise ValueError(f'resample plan for {self.shape_in} images, got {tuple(x.shape)}')
         self.ctx.bind_current_stream()
         x = as_device_f32(x, self.ctx)
-        y = torch.empty(self.shape_out, dtype=torch.float32, device=x.device)
+        y = _result(self.ctx, self.shape_out)
         check(self.ctx.lib.tpz_resample_run(self.handle, _ptr(x), _ptr(y)), self.ctx.handle)
         return y
 
@@ -1038,6 +1076,6 @@ def transpose(x: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     ctx.bind_current_stream()
     x = as_device_f32(x, ctx)
     R, Cc = x.shape
-    y = torch.empty((Cc, R), dtype=torch.float32, device=x.device)
+    y = _result(ctx, (Cc, R))
     check(ctx.lib.tpz_transpose_2d(ctx.handle, _ptr(x), R, Cc, _ptr(y)), ctx.handle)
     return y
