@@ -198,6 +198,33 @@ int tpz_decode(tpz_ctx* ctx, const void* d_raw, int mrc_mode, size_t n, float* d
 enum { TPZ_ENC_F16 = 12, TPZ_ENC_U8 = 8 };
 int tpz_encode(tpz_ctx* ctx, const float* d_in, size_t n, int enc, const float* params, void* d_out,
                unsigned long long* d_overflow);
+/* ---- score tiles: cut, test, paste (predict_in_patches on the device) ------- */
+/* d_tile[z][y][x] = d_x[z0 + z][y0 + y][x0 + x] for the dense [td][th][tw] window of the dense fp32 tensor d_x[D][H][W] at origin
+ * (z0, y0, x0); elements outside the tensor are written as +0.  D = td = 1, z0 = 0 for an image.  The origin may be negative and
+ * the window may reach past the far faces or lie wholly outside (an all-zero tile): this is the zero padding of get_patches
+ * (topaz/model/utils.py:133-169) without the padded copy of the tensor.  The pixels move as 32-bit words (NaN payloads, signed
+ * zeros and subnormals are kept).  Groups of four x take one 16-byte load where the source address is 16-byte aligned and the
+ * group lies inside the row, one 16-byte store where the tile address is; otherwise element by element -- any 4-byte aligned
+ * pointers and any sizes are served.  Nothing outside the td * th * tw floats of d_tile is written.  Refused before anything
+ * is launched: a null pointer, a size < 1, a tile of 2^31 elements or more (or a side above 2^30), an origin beyond +-2^29.
+ * Asynchronous; one launch. */
+int tpz_tile_cut(tpz_ctx* ctx, const float* d_x, int D, int H, int W, int z0, int y0, int x0, int td, int th, int tw,
+                 float* d_tile);
+/* d_flags[t] = 1 when the [td][th][tw] window of d_x[D][H][W] at origin h_origins[3 t .. 3 t + 2] = (z, y, x) holds an element
+ * INSIDE the tensor that is != 0.0f, else 0, for t < n: torch's ne(0).any() of every tile of a grid at once (a NaN counts, -0.0
+ * and what lies outside the tensor do not; a subnormal counts whatever the float mode, the test is on the bits).  The n origins
+ * are on the host and uploaded by the call.  No atomics: whoever sees a non-zero element stores the constant 1.  n == 0 does
+ * nothing.  Refusals as tpz_tile_cut's, and n >= 2^31.  Asynchronous (read d_flags after the stream); one launch. */
+int tpz_tile_flags(tpz_ctx* ctx, const float* d_x, int D, int H, int W, const int* h_origins, size_t n, int td, int th, int tw,
+                   unsigned* d_flags);
+/* canvas[z + k][y + j][x + i] = d_tile[cz + k][cy + j][cx + i] for k < nz, j < ny, i < nx: the box [c, c + n) per axis of the dense
+ * fp32 tile [td][th][tw] pasted into the dense canvas [D][H][W] at (z, y, x), clipped to the canvas (elements that would land
+ * outside it are dropped; the position may be negative).  canvas_f64 == 0: an fp32 canvas, the words are copied; != 0: an fp64
+ * canvas, each value converted (exactly).  16-byte accesses as in tpz_tile_cut, per group of four.  Nothing outside the pasted
+ * box is written.  Refused before anything is launched: a null pointer, a size < 1, a box that is not inside the tile, a tile
+ * of 2^31 elements or more, a position beyond +-2^29.  Asynchronous; one launch. */
+int tpz_tile_paste(tpz_ctx* ctx, const float* d_tile, int td, int th, int tw, int cz, int cy, int cx, int nz, int ny, int nx,
+                   void* d_canvas, int canvas_f64, int D, int H, int W, int z, int y, int x);
 /* 1->1 channel 2-D filter with zero "same" padding: GaussianDenoise / InvGaussianFilter /
  * AffineFilter.forward (topaz/filters.py:28-96).  h_w is the [k][k] kernel on the host. */
 int tpz_filter_2d(tpz_ctx* ctx, const float* d_in, int H, int W, const float* h_w, int k, float bias,

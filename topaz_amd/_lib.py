@@ -95,6 +95,9 @@ _SIGNATURES = {
     'tpz_stage_decode_bytes': (C.c_size_t, [C.c_int, C.c_size_t]),
     'tpz_stage_h2d_decode': (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t]),
     'tpz_encode': (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float), _P, _P]),
+    'tpz_tile_cut': (C.c_int, [_P, _P] + [C.c_int] * 9 + [_P]),
+    'tpz_tile_flags': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P]),
+    'tpz_tile_paste': (C.c_int, [_P, _P] + [C.c_int] * 9 + [_P] + [C.c_int] * 7),
     'tpz_stage_encode_bytes': (C.c_size_t, [C.c_int, C.c_size_t]),
     'tpz_stage_d2h_encode': (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     'tpz_score_2d_host': (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

@@ -25,6 +25,19 @@ _FLOAT16: Flag = (('--float16',), dict(action='store_true',
                                            'beyond +-65504 become inf and are reported on stderr.  MRC output only'))
 _THREADS: Flag = (('-j', '--num-threads'), dict(type=int, default=0, help='host threads for torch (0: library default, <0: all cores)'))
 
+# the fit of `--preprocess` (extract, segment): the flags of `topaz preprocess` under a prefix
+_PREPROCESS_FIT: List[Flag] = [
+    (('--preprocess-affine',), dict(action='store_true', help='--preprocess: plain (x - mean) / std instead of the mixture fit '
+                                                              '(`topaz preprocess --affine`)')),
+    (('--preprocess-sample',), dict(type=int, default=10, help='--preprocess: fit the mixture on every n-th pixel '
+                                                               '(`topaz preprocess --sample`)')),
+    (('--preprocess-niters',), dict(type=int, default=100, help='--preprocess: cap on the EM iterations of one fit (`--niters`)')),
+    (('--preprocess-alpha',), dict(type=float, default=900, help='--preprocess: alpha of the Beta prior on the mixing proportion '
+                                                                 '(`--alpha`)')),
+    (('--preprocess-beta',), dict(type=float, default=1, help='--preprocess: beta of the Beta prior on the mixing proportion '
+                                                              '(`--beta`)')),
+]
+
 EXTRACT: List[Flag] = [
     (('paths',), dict(nargs='*', help='micrographs to pick from; read from stdin when empty')),
     (('-m', '--model'), dict(default='resnet16', help='pretrained alias, model file, or "none" when the inputs already are score maps')),
@@ -57,15 +70,7 @@ EXTRACT: List[Flag] = [
                                   '(0: off; 1: normalise only).  Picks are in the frame of the scored, S times smaller image, '
                                   'exactly as when `topaz preprocess` wrote it to a file first: -x S scales them back to the raw '
                                   'frame.  Needs --dims 2 and a model')),
-    (('--preprocess-affine',), dict(action='store_true', help='--preprocess: plain (x - mean) / std instead of the mixture fit '
-                                                              '(`topaz preprocess --affine`)')),
-    (('--preprocess-sample',), dict(type=int, default=10, help='--preprocess: fit the mixture on every n-th pixel '
-                                                               '(`topaz preprocess --sample`)')),
-    (('--preprocess-niters',), dict(type=int, default=100, help='--preprocess: cap on the EM iterations of one fit (`--niters`)')),
-    (('--preprocess-alpha',), dict(type=float, default=900, help='--preprocess: alpha of the Beta prior on the mixing proportion '
-                                                                 '(`--alpha`)')),
-    (('--preprocess-beta',), dict(type=float, default=1, help='--preprocess: beta of the Beta prior on the mixing proportion '
-                                                              '(`--beta`)')),
+    *_PREPROCESS_FIT,
     (('--particle-stack',), dict(metavar='PATH',
                                  help='also write the MRC particle stack `topaz particle_stack` would make of the pick table, and '
                                       'its STAR file next to it, cut while each micrograph is resident for picking (under '
@@ -166,6 +171,16 @@ SEGMENT: List[Flag] = [
     (('-v', '--verbose'), dict(action='store_true', help='progress on stdout')),
     _GPUS,
     _PRECISION,
+    (('--preprocess',), dict(type=int, default=0, metavar='S',
+                             help='score raw micrographs: put every input through what `topaz preprocess -s S` does -- Fourier '
+                                  'down-sampling by S (when S > 1), then normalisation -- in device memory before it is scored '
+                                  '(0: off; 1: normalise only).  The map has the size of the S times smaller image.  Micrographs '
+                                  'only, not volumes')),
+    *_PREPROCESS_FIT,
+    (('--format',), dict(choices=['tiff', 'mrc', 'npy'], default=None,
+                         help='file type of the score maps (default: tiff for micrographs, npy for volumes); mrc carries the '
+                              'header of an MRC input with its mode and size updated')),
+    _FLOAT16,
 ]
 
 DOWNSAMPLE: List[Flag] = [

@@ -21,6 +21,7 @@
 //   rt_nms.hip      the NMS driver
 //   rt_particles.hip  particle stacks: batched crop / standardise and frame resize (its kernels live there too)
 //   rt_prefilter.hip  denoise pre-filters: fp64 low-pass GEMMs, tile covariances, the per-tile deconvolution filter (kernels there too)
+//   rt_tiles.hip      score tiles: the zero-padded window cut, the all-zero flags of a tile grid, the cropped paste (kernels there too)
 //   rt_resample.hip   the truncated-DFT resampler: plans with device-resident operators over the fp32-MFMA GEMM of resample_gemm.h
 // Workspace ownership: temporary device memory is held by a WorkBuf (below), never by a bare pointer.  The handle takes its buffer
 // from the pool that is current at that moment and remembers THAT pool, so its release -- scope exit, or release() where a

@@ -36,7 +36,7 @@ from . import parallel
 from .algorithms import match_coordinates, non_maximum_suppression, non_maximum_suppression_3d
 from .metrics import average_precision
 from .model.factory import load_model
-from .model.utils import predict_in_patches
+from .model.utils import predict_in_patches_device
 from .precision import check_loaded_model
 from .streaming import ImageFeed
 from .utils import files as file_utils
@@ -219,20 +219,20 @@ class Scorer:
         self.precision = check_loaded_model(self.model, precision_check, model, verbose)
 
     def __call__(self, image: torch.Tensor, patch_size: int = 0):
-        """[H, W] / [D, H, W] device tensor -> logits of the same shape (device tensor; float64 numpy when patched, like
-        predict_in_patches upstream)"""
-        x = image[None, None]
+        """[H, W] / [D, H, W] device tensor -> logits of the same shape, a float32 device tensor; patched: the map
+        predict_in_patches stitches, left where the suppression reads it (its float64 values are these float32 numbers)"""
         if patch_size:
             halo = self.model.width // 2
-            return predict_in_patches(self.model, x, patch_size + 2 * halo, is_3d=(image.dim() == 3), use_cuda=True)[0, 0]
+            return predict_in_patches_device(self.model, image, patch_size + 2 * halo, is_3d=(image.dim() == 3))
         with torch.no_grad():
-            return self.model(x)[0, 0]
+            return self.model(image[None, None])[0, 0]
 
 
 def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int = 0, batch_size: int = 1,
                  keep_on_device: bool = False, precision_check: str = 'never',
                  verbose: bool = False, preprocess=None, with_image: bool = False) -> Iterator[Tuple[str, np.ndarray]]:
-    """generator of (path, score map).  `model` None / 'none': the inputs already are score maps and pass through.
+    """generator of (path, score map).  `model` None / 'none': the inputs already are score maps (what `segment` wrote: TIFF,
+    MRC, .npy volumes) and pass through -- under keep_on_device through the ImageFeed, as device tensors of their own.
     keep_on_device=True yields device tensors (no PCIe round trip before the suppression).  precision_check / verbose: the
     `--precision-check` mode of the loaded model (Scorer).  preprocess: a callable device tensor -> device tensor (e.g.
     stats.DevicePreprocess) applied to every image the feed yields before it is scored -- here, in the consuming thread and in
@@ -245,8 +245,20 @@ def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int =
             raise ValueError('preprocess needs a model: score maps are not micrographs')
         if with_image:
             raise ValueError('with_image needs a model: score maps are not micrographs')
-        for path in paths:
-            yield path, load_image(path, make_image=False, return_header=False)
+        if not keep_on_device:
+            for path in paths:
+                yield path, _load_map(path)
+            return
+        # the maps take the road micrographs take: the feed's reader thread reads map i+1 (an MRC file in the type it stores,
+        # decoded on the device; TIFF through PIL; a .npy volume as an item in memory) under the suppression of map i.  Each is
+        # copied out of its staging slot, which the feed re-uses: the caller may keep every map (`--targets`)
+        from . import runtime as rt
+        if device is not None and device < 0:
+            raise RuntimeError('topaz_amd has no CPU path: use -d >= 0 (an MI355X)')
+        torch.cuda.set_device(device)
+        items = [(p, np.load(p, mmap_mode='r'), None, None) if os.path.splitext(p)[1] == '.npy' else p for p in paths]
+        for path, scores in ImageFeed(items, rt.get_context(device)):
+            yield path, scores.clone()
         return
     scorer = Scorer(model, device, precision_check, verbose)
     for item in (ImageFeed(paths, scorer.ctx, headers=True) if with_image else ImageFeed(paths, scorer.ctx)):
@@ -255,10 +267,19 @@ def score_images(model, paths: Iterable[str], device: int = 0, patch_size: int =
         scores = scorer(image, patch_size)
         if torch.is_tensor(scores) and not keep_on_device:
             scores = scores.cpu().numpy()
+            if patch_size:
+                scores = scores.astype(np.float64)               # (what predict_in_patches returns, upstream and here)
         if with_image:
             yield path, scores, raw, item[2]
         else:
             yield path, scores
+
+
+def _load_map(path: str) -> np.ndarray:
+    """a score map on the host: an image file, or the .npy volume `segment` writes of a tomogram"""
+    if os.path.splitext(path)[1] == '.npy':
+        return np.load(path)
+    return load_image(path, make_image=False, return_header=False)
 
 
 def _keep_resident(items, resident: list):

@@ -886,6 +886,74 @@ def encode(x: torch.Tensor, enc: int, params=None, ctx: Optional[Context] = None
     return out, (int(counter.item()) if counter is not None else (0 if count else None))
 
 
+def _dense_f32(x: torch.Tensor, ctx: Context, what: str) -> Tuple[torch.Tensor, int, int, int]:
+    """a 2-D or 3-D tensor as the dense fp32 device tensor the tile entry points read (a contiguous view stays the view it is),
+    with its (D, H, W)"""
+    if x.dim() not in (2, 3):
+        raise ValueError(f'{what}: a [H, W] or [D, H, W] tensor is needed, got {tuple(x.shape)}')
+    x = as_device_f32(x, ctx)
+    return (x, 1) + tuple(x.shape) if x.dim() == 2 else (x,) + tuple(x.shape)
+
+
+def _zyx(v, dims: int, z: int) -> Tuple[int, int, int]:
+    """(z, y, x) of a per-axis triple or pair given in the order of the tensor's axes; the given z for an image"""
+    v = tuple(int(a) for a in v)
+    if len(v) != dims:
+        raise ValueError(f'{dims} coordinates are needed, got {v}')
+    return v if dims == 3 else (z,) + v
+
+
+def tile_cut(x: torch.Tensor, origin, size, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_tile_cut: the window of `size` = ([td,] th, tw) of the [D,] H, W tensor x at `origin` = ([z0,] y0, x0) as a dense
+    tensor of its own, zero where the window leaves x (the origin may be negative, the window may reach past x or miss it).
+    One launch, asynchronous."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x, D, H, W = _dense_f32(x, ctx, 'tile_cut')
+    dims = x.dim()
+    z0, y0, x0 = _zyx(origin, dims, 0)
+    td, th, tw = _zyx(size, dims, 1)
+    if min(td, th, tw) < 1:
+        raise ValueError(f'tile_cut: size {tuple(size)} must be positive')
+    y = _result(ctx, (td, th, tw)[3 - dims:])
+    check(ctx.lib.tpz_tile_cut(ctx.handle, _ptr(x), D, H, W, z0, y0, x0, td, th, tw, _ptr(y)), ctx.handle)
+    return y
+
+
+def tile_flags(x: torch.Tensor, origins, size, ctx: Optional[Context] = None) -> torch.Tensor:
+    """tpz_tile_flags: int32 device tensor [n], 1 where the window of `size` at origins[t] holds an element of x that is != 0
+    (torch's ne(0): NaN counts, -0.0 and what lies outside x do not), for all n windows in ONE launch.  Asynchronous: the
+    caller reads the flags back (one .cpu()) when it needs them."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    x, D, H, W = _dense_f32(x, ctx, 'tile_flags')
+    dims = x.dim()
+    td, th, tw = _zyx(size, dims, 1)
+    org = np.ascontiguousarray([_zyx(o, dims, 0) for o in origins], dtype=np.int32).reshape(-1, 3)
+    flags = _result(ctx, (len(org),), torch.int32)
+    check(ctx.lib.tpz_tile_flags(ctx.handle, _ptr(x), D, H, W, org.ctypes.data_as(C.c_void_p), len(org), td, th, tw, _ptr(flags)),
+          ctx.handle)
+    return flags
+
+
+def tile_paste(tile: torch.Tensor, crop, extent, canvas: torch.Tensor, at, ctx: Optional[Context] = None) -> None:
+    """tpz_tile_paste: the box [crop, crop + extent) per axis of the fp32 tile goes into `canvas` (a contiguous float32 or float64
+    device tensor of the tile's dimensionality) at `at`, clipped to the canvas; nothing else of the canvas is written.
+    One launch, asynchronous."""
+    ctx = ctx or get_context()
+    ctx.bind_current_stream()
+    tile, td, th, tw = _dense_f32(tile, ctx, 'tile_paste')
+    dims = tile.dim()
+    if not (canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == dims and canvas.dtype in (torch.float32, torch.float64)):
+        raise _lib.TopazHipError('tile_paste: the canvas must be a contiguous float32 / float64 device tensor of the tile\'s rank')
+    D, H, W = tuple(canvas.shape) if dims == 3 else (1,) + tuple(canvas.shape)
+    cz, cy, cx = _zyx(crop, dims, 0)
+    nz, ny, nx = _zyx(extent, dims, 1)
+    z, y, x = _zyx(at, dims, 0)
+    check(ctx.lib.tpz_tile_paste(ctx.handle, _ptr(tile), td, th, tw, cz, cy, cx, nz, ny, nx, _ptr(canvas),
+                                 1 if canvas.dtype == torch.float64 else 0, D, H, W, z, y, x), ctx.handle)
+
+
 def normalize_cutoff(x: torch.Tensor, mean: float, std: float, cutoff: float, ctx: Optional[Context] = None) -> torch.Tensor:
     """normalize() with denoise_image's pixel cutoff fused (tpz_normalize_cutoff): v = (x - mean) / std, then 0 where
     v < -cutoff or v > cutoff, compared in fp32; NaN passes, +-inf is zeroed; cutoff <= 0 is normalize()"""
